@@ -10,9 +10,13 @@ block (world_size > 1).  value = reads processed by all ranks / max-over-ranks t
 Prints ONE JSON line on rank 0 (see the task contract), including
   roofline     algorithmic bytes (2L + 4 + 8 per read) / average kernel time measured with HIP
                events on the library's compute stream; peak = 8 TB/s HBM3E
+and, with --full only (a plain run sets up, warms up, times the steps and prints the line):
   cpu_baseline the real reference binary (oracle/_ref/FaQCs_ref -t <cores>, kind "reference") or the plain-C
                port (kind "port") timed on a bounded sample of the same workload on this host.
   e2e          (N = 1, plain / adapter) faqcs_mi from FASTQ files in /dev/shm to trimmed FASTQ + QC.stats.txt, reads/s.
+  configs      (N = 1, plain 2x150) BASELINE's adapter and k-mer configurations and --replace_to_N_q, two steps each.
+  config.value_without_terminal_n_flags, and the full-size consistency checks of the counter block (verify_full_size).
+--dump-outputs DIR writes what the last timed step computed (dump_outputs) for output-for-output comparisons of two builds.
 
 --gpus N without WORLD_SIZE in the environment: this process starts N rank processes (before it touches the GPU) and relays
 rank 0's line; under torch.distributed.run it reads RANK / LOCAL_RANK / WORLD_SIZE.  --config kmer --gpus N runs the
@@ -52,13 +56,18 @@ def parse():
                     "reads dinucleotide candidates of the low-complexity filter (an AT-rich genome)")
     ap.add_argument("--kmer-table-log2", type=int, default=31, help="log2 of the k-mer table's slots per GPU (--config kmer; 2^31 slots = 34 GB: the "
                     "tests that put eight ranks on one GPU pass 24)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="besides the headline: the full-size consistency checks of the counter block, the "
+                    "same job without terminal_n flags, the CPU baseline, the end-to-end run of faqcs_mi and (N = 1, config plain, 2x150) "
+                    "BASELINE's other configurations; a plain run only sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last step computed as DIR/<name>.npy "
+                    "(float32 / float64): the counter block, a fixed sample of the per-read results and their column sums over every read")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) no CPU baseline")
     ap.add_argument("--dry-run-memory", action="store_true", help="--config kmer: print every rank's HBM budget (reads, table, group buffers: "
                     "faqcs_kmer_memory_plan) and stop before anything is allocated; exit 1 when a rank's share of its device cannot hold it")
-    ap.add_argument("--no-other-configs", action="store_true", help="the default single-GPU run (config plain, 2x150) also runs BASELINE's adapter and k-mer "
+    ap.add_argument("--no-other-configs", action="store_true", help="the --full single-GPU run (config plain, 2x150) also runs BASELINE's adapter and k-mer "
                     "configurations, two steps each, and reports them under \"configs\"; this switches that off")
     ap.add_argument("--e2e-pairs", type=float, default=float(os.environ.get("FAQCS_BENCH_E2E_PAIRS", -1)),
-                    help="pairs of the same workload written as FASTQ to /dev/shm for the end-to-end (files in, files out) run of faqcs_mi; 0 = skip; "
+                    help="(--full) pairs of the same workload written as FASTQ to /dev/shm for the end-to-end (files in, files out) run of faqcs_mi; 0 = skip; "
                          "default: 16 M pairs when /dev/shm has 64 GB free (20 GB of files; the fixed 0.4 s of HIP start-up weighs less), else 8 M")
     return ap.parse_args()
 
@@ -293,6 +302,8 @@ def main():
     os.dup2(2, 1)
     if a.gpus < 1:
         raise SystemExit("bench: --gpus must be >= 1")
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("bench: --steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         launch_ranks(a, real_stdout)  # (does not return)
     import torch
@@ -332,15 +343,18 @@ def main():
         dist.barrier()
 
     env = {"rank": rank, "world": world, "local": local, "dev": dev, "use_dist": use_dist, "backend": backend, "real_stdout": real_stdout}
-    if a.e2e_pairs < 0:
+    if not a.full:
+        a.e2e_pairs = 0
+    elif a.e2e_pairs < 0:
         try:
             import shutil
 
             a.e2e_pairs = 16e6 if shutil.disk_usage("/dev/shm").free > 64e9 else 8e6
         except OSError:
             a.e2e_pairs = 8e6
-    out, keep = run_workload(env, a, a.config, a.pairs, a.steps, a.warmup, a.read_len, want_host_sample=(rank == 0 and world == 1))
-    if rank == 0:
+    out, keep = run_workload(env, a, a.config, a.pairs, a.steps, a.warmup, a.read_len, want_host_sample=(a.full and rank == 0 and world == 1),
+                             dump_dir=a.dump_outputs if rank == 0 else None)
+    if rank == 0 and a.full:
         L = out["config"]["read_len"]
         opt_args = keep["opt_args"]
         if world == 1 and not a.no_cpu_baseline:
@@ -351,9 +365,9 @@ def main():
             ne = int(min(a.e2e_pairs, keep["sample_reads"] // 2))
             out["e2e"] = e2e_run(opt_args, keep["hs"][: 2 * ne * L], keep["hq"][: 2 * ne * L], L, ne)
     keep.clear()
-    # The other single-GPU configurations of BASELINE.json, at their sizes, next to the headline (N = 1, default invocation):
+    # The other single-GPU configurations of BASELINE.json, at their sizes, next to the headline (N = 1, --full):
     # configs[2] (--adapter --polyA on 100 M pairs) and configs[4]'s per-GPU share (25 M pairs 2x250 --kmer_rarefaction)
-    if world == 1 and a.config == "plain" and a.read_len is None and not a.no_other_configs:
+    if a.full and world == 1 and a.config == "plain" and a.read_len is None and not a.no_other_configs:
         others = {}
         for cfg in ("adapter", "kmer"):
             try:
@@ -442,9 +456,45 @@ def verify_full_size(blk, lay, fs, results, n_reads, L, config, n_adapters):
             fail("reads credited to adapter %d vs adapter_stats" % j, h[j], st[j])
 
 
-def run_workload(env, a, config, pairs, steps, warmup, read_len, want_host_sample):
+def dump_outputs(dump_dir, blk, results, n_reads, config, eng, steps_run):
+    """--dump-outputs: what the last step handed its caller, as float32 / float64 .npy files (about 26 MB at most):
+    counters.npy                the job's counter block (u64 words, all-reduced over the ranks);
+    results_sample.npy          [k, 4] per-read results (start, kept, flags, 1 + credited adapter) of k = min(n, 2^20) reads of this
+                                rank's data set, chosen by a fixed seed;  results_sample_index.npy: their read indices;
+    results_column_sums.npy     [4] the sums of the four result columns over every read of this rank;
+    kmer_totals.npy, kmer_points.npy  (--config kmer in one process) distinct / total k-mers of the pass and its rarefaction points."""
+    import torch
+
+    os.makedirs(dump_dir, exist_ok=True)
+    k = min(n_reads, 1 << 20)
+    idx = np.sort(np.random.default_rng(20260101).choice(n_reads, size=k, replace=False))
+    sample = np.empty((k, 4), np.float32)
+    sums = np.zeros(4, np.float64)
+    lo = 0
+    for r in results:
+        m = r.shape[0]
+        u = r.to(torch.int32) & 0xffff
+        sums += u.sum(dim=0, dtype=torch.int64).cpu().numpy()
+        a, b = np.searchsorted(idx, [lo, lo + m])
+        if b > a:
+            sel = torch.from_numpy(idx[a:b] - lo).to(r.device)
+            sample[a:b] = u.index_select(0, sel).cpu().numpy()
+        lo += m
+    files = {"counters": blk.astype(np.float64), "results_sample": sample, "results_sample_index": idx.astype(np.float64),
+             "results_column_sums": sums}
+    if config == "kmer" and eng is not None:
+        files["kmer_totals"] = np.array(eng.kmer_totals(), np.float64)
+        pts = eng.kmer_points()
+        per = len(pts) // max(1, steps_run)  # (the points accumulate over the steps: the last step's are the last `per`)
+        pts = pts[len(pts) - per:]
+        files["kmer_points"] = np.stack([pts[f].astype(np.float64) for f in pts.dtype.names], axis=1) if per else np.zeros((0, 3))
+    for name, arr in files.items():
+        np.save(os.path.join(dump_dir, name + ".npy"), arr)
+
+
+def run_workload(env, a, config, pairs, steps, warmup, read_len, want_host_sample, dump_dir=None):
     """One configuration: builds the resident data set, times `steps` steps, returns (the JSON object, a dict with a host
-    sample of the data for the CPU baseline / the end-to-end run).  Frees its device memory before it returns."""
+    sample of the data for the CPU baseline / the end-to-end run).  dump_dir: --dump-outputs.  Frees its device memory before it returns."""
     import torch
 
     from faqcs_amd import _capi as capi
@@ -681,14 +731,16 @@ def run_workload(env, a, config, pairs, steps, warmup, read_len, want_host_sampl
     fs = blk[lay["filter_stats"][0]:lay["filter_stats"][0] + 32]
     if int(fs[capi.TOTAL_NUMBER]) != n_reads * world or int(fs[capi.TOTAL_LENGTH]) != n_reads * world * L:
         raise SystemExit("bench: counter block does not add up: %d reads counted, %d expected" % (int(fs[capi.TOTAL_NUMBER]), n_reads * world))
-    # ... and, at the job's full size, the accumulators must agree with each other and with the per-read results (size-independent
+    if dump_dir:
+        dump_outputs(dump_dir, blk, [bb[3] for bb in batches], n_reads, config, eng if kx is None else None, steps + warmup)
+    # (--full) ... and, at the job's full size, the accumulators must agree with each other and with the per-read results (size-independent
     # properties: the oracle compares every counter on batches it can finish, tests/test_gpu_parity.py; this is the same block on 2 x 10^8 reads)
-    if world == 1:
+    if a.full and world == 1:
         verify_full_size(blk, lay, fs, [bb[3] for bb in batches], n_reads, L, config, eng.holder.n_adapters)
-    # the same job with batches that carry no terminal_n flags (the kernel then looks at the two end bases of every read itself):
+    # (--full) the same job with batches that carry no terminal_n flags (the kernel then looks at the two end bases of every read itself):
     # outside the timed region, reported beside the headline so that the effect of the flags is visible
     noflag_value = None
-    if world == 1 and config == "plain":
+    if a.full and world == 1 and config == "plain":
         fence()
         t1 = time.perf_counter()
         for _ in range(2):

@@ -10,7 +10,7 @@ out=gpurun_out/$tag
 mkdir -p $out
 export TMPDIR=/tmp
 if [ "${SKIP_BENCH:-0}" != 1 ]; then
-python3 bench.py > $out/bench_plain_100Mpairs.json 2> $out/bench_plain.err
+python3 bench.py --full > $out/bench_plain_100Mpairs.json 2> $out/bench_plain.err
 FAQCS_BENCH_SHARE_GPU=1 python3 bench.py --gpus 2 --pairs 10e6 --no-cpu-baseline --e2e-pairs 0 > $out/bench_plain_2ranks_shared_gpu.json 2>> $out/bench_plain.err  # (FAQCS_BENCH_SHARE_GPU=1 in the environment: the launch path, not a measurement)
 python3 bench.py --config adapter --pairs 20e6 --no-cpu-baseline --e2e-pairs 0 > $out/bench_adapter_20Mpairs.json 2> $out/bench_adapter.err
 python3 bench.py --read-len 250 --pairs 40e6 --no-cpu-baseline --e2e-pairs 0 > $out/bench_plain_250bp_40Mpairs.json 2>> $out/bench_plain.err

@@ -9,8 +9,8 @@ mkdir -p $out
 export TMPDIR=/tmp
 b() { python3 bench.py "$@" 2>> $out/bench.err; }
 # 1. bench lines: the three BASELINE configurations at BASELINE's sizes, then other read lengths through the same harness
-b > $out/bench_plain_100Mpairs.json
-b --config adapter --e2e-pairs 0 > $out/bench_adapter_100Mpairs.json
+b --full > $out/bench_plain_100Mpairs.json
+b --full --config adapter --e2e-pairs 0 > $out/bench_adapter_100Mpairs.json
 b --config kmer --no-cpu-baseline > $out/bench_kmer_250bp_25Mpairs.json
 for L in 100 125 250 300; do b --read-len $L --pairs 40e6 --no-cpu-baseline --e2e-pairs 0 > $out/bench_plain_${L}bp_40Mpairs.json; done
 for L in 50 75 128; do b --read-len $L --pairs 60e6 --no-cpu-baseline --e2e-pairs 0 > $out/bench_plain_${L}bp_60Mpairs.json; done

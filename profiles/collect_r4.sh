@@ -8,7 +8,7 @@ mkdir -p $out
 export TMPDIR=/tmp
 b() { python3 bench.py "$@" 2>> $out/bench.err; }
 # 1. the driver's command: the headline + BASELINE's adapter and k-mer configurations + cpu_baseline (best of -t 1/8/16/all) + e2e
-b > $out/bench_default_all_configs.json
+b --full > $out/bench_default_all_configs.json
 # 2. other shapes through the same harness
 for L in 100 125 192 200 250 251 300; do b --read-len $L --pairs 40e6 --no-cpu-baseline --e2e-pairs 0 --no-other-configs > $out/bench_plain_${L}bp_40Mpairs.json; done
 for L in 96 128; do b --read-len $L --pairs 60e6 --no-cpu-baseline --e2e-pairs 0 --no-other-configs > $out/bench_plain_${L}bp_60Mpairs.json; done

@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 out=gpurun_out/${1:-r6u}
 mkdir -p $out
 for i in 1 2 3 4 5; do
-  timeout 600 python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-other-configs 2>> $out/bench.err < /dev/null | python3 -c "
+  timeout 600 python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-other-configs 2>> $out/bench.err < /dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); e=d['e2e']
 print('run $i: one process %.1f, as the caller sees it %.1f, pipeline %.1f M reads/s; marks %s' % (e['value'], e['value_as_the_caller_sees_it'], e['pipeline_value'], json.dumps(e['stage_marks_s'])))"
