@@ -143,33 +143,41 @@ __device__ __forceinline__ uint32_t first_word_max(const uint32_t (&R)[4][2 * NB
     return m;
 }
 
+// The winner of a diagonal block is the largest (i, j) among its cells of maximal M, packed as (i << KEY_JBITS | j) + 1: 15 bits of
+// target coordinate (targets of up to FAQCS_MAX_ADAPTER_LENGTH = 32 767 bases) above 15 bits of read coordinate, plus one, fit 32 bits.
+constexpr uint32_t KEY_JBITS = 15, KEY_JMASK = (1u << KEY_JBITS) - 1u;
+constexpr int BB_CAP = 136; // per-block bounds s_bb holds: |read| <= 320 and |target| <= FAQCS_ADAPTER_SINGLE_LENGTH -> 8 511 diagonals
+
 #ifndef FAQCS_ADAPTER_WAVES
 #define FAQCS_ADAPTER_WAVES 4 /* waves per SIMD the 256-base variant is compiled for (5 = 96 VGPRs with 12 spilled: measured, no faster) */
 #endif
-template <int NW, int MAXLEN>
+// GROUPED: A is one group of a larger library (faqcs_dev.h); the read's state comes from G.state and goes back there, and only the last
+// group's launch finishes the read.  Without GROUPED (a set of at most 64 targets of at most 8 192 bases) G is unused.
+template <int NW, int MAXLEN, bool GROUPED = false>
 __global__ __launch_bounds__(NW * 64, MAXLEN == 320 ? 3 : (MAXLEN == 256 ? FAQCS_ADAPTER_WAVES : 4)) void adapter_overlap(
     const AdapterDev A, const uint8_t *__restrict__ seq, const uint32_t *__restrict__ off, const uint32_t n_reads,
     const uint32_t *__restrict__ seg_start, const uint32_t n_segments, uint32_t *__restrict__ ad_sl,
-    uint16_t *__restrict__ ad_hit, uint64_t *__restrict__ adapter_stats, uint32_t *__restrict__ err, const uint32_t dbg)
+    uint16_t *__restrict__ ad_hit, uint64_t *__restrict__ adapter_stats, uint32_t *__restrict__ err, const uint32_t dbg,
+    const AdapterGroup G)
 {
     constexpr int QW = MAXLEN / 32;            // data dwords per plane
     constexpr int PADL = MAXLEN == 320 ? 14 : 12; // zero dwords on each side: the register-blocked stage 1 reads up to PADL dwords
     constexpr int PW = QW + 2 * PADL;          // before / after the data without clamping its index
-    constexpr int TPL_CAP = 4096;              // adapter plane dwords cached in LDS (16 KB: every built-in set incl. PhiX)
+    constexpr int TPL_CAP = FAQCS_ADAPTER_TPL_CAP;              // adapter plane dwords cached in LDS (16 KB: every built-in set incl. PhiX)
     constexpr int NBLK = 6;                    // 64-diagonal blocks kept in registers: |read| <= 256, |adapter| <= 128
     __shared__ uint8_t s_q[NW][MAXLEN];        // the read's IUPAC masks (stage 2)
     __shared__ uint8_t s_mask[NW][MAXLEN];     // vector<bool> mask of trim.cpp:991 (1 = unmasked)
     __shared__ uint32_t s_pl[NW][4][PW];       // the read's four base bit-planes, position ordered (stage 1)
     __shared__ __attribute__((aligned(16))) uint32_t s_tpl[TPL_CAP]; // the adapters' bit-planes (4 dwords per 32 bases)
-    __shared__ uint8_t s_sb[NW][FAQCS_MAX_ADAPTERS][8]; // stage 1 -> stage 2: per 64-diagonal block, an upper bound of its best score (short adapters that may pass)
-    __shared__ uint32_t s_bb[NW][136];         // stage 2 on long targets: per 64-diagonal block, an upper bound of its best score
-    __shared__ uint32_t s_ast[2 * FAQCS_MAX_ADAPTERS]; // (reads, bases) credited per adapter by this block
+    __shared__ uint8_t s_sb[NW][FAQCS_ADAPTER_GROUP][8]; // stage 1 -> stage 2: per 64-diagonal block, an upper bound of its best score (short adapters that may pass)
+    __shared__ uint32_t s_bb[NW][BB_CAP];      // stage 2 on long targets: per 64-diagonal block, an upper bound of its best score
+    __shared__ uint32_t s_ast[2 * FAQCS_ADAPTER_GROUP]; // (reads, bases) credited per adapter by this block (GROUPED: unused)
     __shared__ uint8_t s_iupac[32];
     __shared__ uint8_t s_na[256];              // na_to_bits() of every byte value (0 = the reference throws)
-    __shared__ uint32_t s_start[FAQCS_MAX_ADAPTERS + 1], s_wstart[FAQCS_MAX_ADAPTERS + 1]; // adapter table of contents
-    __shared__ __attribute__((aligned(16))) uint4 s_meta[FAQCS_MAX_ADAPTERS]; // {|adapter|, first plane word, int(rate * |adapter|), base planes present}
-    __shared__ uint32_t s_pos[FAQCS_MAX_ADAPTERS];      // adapter -> position in the class order
-    __shared__ uint32_t s_ord[FAQCS_MAX_ADAPTERS + 8];  // stage 1 visits the adapters class by class (1, 2, 3, 4 plane words; the rest): position -> adapter,
+    __shared__ uint32_t s_start[FAQCS_ADAPTER_GROUP + 1], s_wstart[FAQCS_ADAPTER_GROUP + 1]; // adapter table of contents
+    __shared__ __attribute__((aligned(16))) uint4 s_meta[FAQCS_ADAPTER_GROUP]; // {|adapter|, first plane word, int(rate * |adapter|), base planes present}
+    __shared__ uint32_t s_pos[FAQCS_ADAPTER_GROUP];      // adapter -> position in the class order
+    __shared__ uint32_t s_ord[FAQCS_ADAPTER_GROUP + 8];  // stage 1 visits the adapters class by class (1, 2, 3, 4 plane words; the rest): position -> adapter,
                                                         // then [64 + c] = first position of class c + 1 ... (stage 1 is order-free: it only sets flags)
     const int lane = threadIdx.x & 63;
     const int wave = uni(threadIdx.x >> 6);
@@ -186,7 +194,7 @@ __global__ __launch_bounds__(NW * 64, MAXLEN == 320 ? 3 : (MAXLEN == 256 ? FAQCS
     const bool tpl_cached = uni((int)(tpl_dwords <= (uint32_t)TPL_CAP)) != 0; // (uni: the branches on it stay scalar branches)
     if (tpl_cached) for (uint32_t i = threadIdx.x; i < tpl_dwords; i += NW * 64) s_tpl[i] = A.planes[i];
     if (threadIdx.x < 32) s_iupac[threadIdx.x] = threadIdx.x < 26 ? k_iupac[threadIdx.x] : (uint8_t)0;
-    for (uint32_t i = threadIdx.x; i < 2 * FAQCS_MAX_ADAPTERS; i += NW * 64) s_ast[i] = 0u;
+    for (uint32_t i = threadIdx.x; i < 2 * FAQCS_ADAPTER_GROUP; i += NW * 64) s_ast[i] = 0u;
     for (uint32_t i = threadIdx.x; i < A.n_adapters; i += NW * 64) {
         const uint32_t tl = A.start[i + 1] - A.start[i];
         uint32_t amask = 0; // which of the four base planes the adapter has a bit in (any_match below)
@@ -207,7 +215,7 @@ __global__ __launch_bounds__(NW * 64, MAXLEN == 320 ? 3 : (MAXLEN == 256 ? FAQCS
             const uint64_t m = __ballot(cls == c);
             if (cls == c) { const uint32_t at = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull)); s_ord[at] = (uint32_t)lane; s_pos[lane] = at; }
             base += (uint32_t)__popcll(m);
-            if (lane == 0) s_ord[FAQCS_MAX_ADAPTERS + c] = base; // end of class c
+            if (lane == 0) s_ord[FAQCS_ADAPTER_GROUP + c] = base; // end of class c
         }
     }
     __syncthreads();
@@ -303,17 +311,20 @@ __global__ __launch_bounds__(NW * 64, MAXLEN == 320 ? 3 : (MAXLEN == 256 ? FAQCS
         const uint32_t rmask = (pm0 ? 1u : 0u) | (pm1 ? 2u : 0u) | (pm2 ? 4u : 0u) | (pm3 ? 8u : 0u);
         lds_sync_wave();
         // exact alignment of adapter j: best (M, i, j) over all diagonals -> (score or -1, start, stop)
-        auto align_exact = [&](uint32_t j, int &gM, int &gS, int &gI) {
-            const uint32_t t0 = s_start[j];
-            const int tlen = (int)(s_start[j + 1] - t0);
+        // (outside: j is the GLOBAL index of a target of an earlier group -- GROUPED only, the H2 stale range of a target that is no longer in
+        // LDS -- aligned without the bound pass, from global memory)
+        auto align_exact = [&](uint32_t j, int &gM, int &gS, int &gI, const bool outside = false) {
+            const uint32_t t0 = outside ? G.gstart[j] : s_start[j];
+            const int tlen = (int)((outside ? G.gstart[j + 1] : s_start[j + 1]) - t0);
             gM = -1; gI = 0; gS = 0;
             int gJ = 0;
             const int ndiag = qlen + tlen - 1;
             // A local alignment scores at most the number of matches on its diagonal, so the largest per-diagonal match
             // count of a 64-diagonal block bounds every cell of the block (87 blocks for PhiX, 3-4 for the built-in adapters).  The block with the largest
             // bound is aligned first; a block whose bound is below the best score so far cannot win (ties are decided by
-            // the explicit (M, i, j) comparison below, so the visiting order is free).
-            const bool pruned = MAXLEN <= 320 && tpl_cached;
+            // the explicit (M, i, j) comparison below, so the visiting order is free).  (GROUPED: a target of more than BB_CAP blocks is
+            // aligned unpruned -- diagonals are independent, so the result is the same.)
+            const bool pruned = MAXLEN <= 320 && tpl_cached && !outside && (!GROUPED || ndiag <= 64 * BB_CAP);
             constexpr int NBX = MAXLEN == 320 ? 7 : 6, NAX = NBX + 1; // window blocks / accumulators of the sliding bound pass
             uint32_t *bb = s_bb[wave];
             int first_block = 0;
@@ -387,9 +398,9 @@ __global__ __launch_bounds__(NW * 64, MAXLEN == 320 ? 3 : (MAXLEN == 256 ? FAQCS
                 }
                 const int Mx = (int)wave_max_u32((uint32_t)(bM + 1)) - 1;
                 if (Mx >= 0) {
-                    const uint32_t key = (bM == Mx) ? ((((uint32_t)bI << 13) | (uint32_t)(bI + d)) + 1u) : 0u;
+                    const uint32_t key = (bM == Mx) ? ((((uint32_t)bI << KEY_JBITS) | (uint32_t)(bI + d)) + 1u) : 0u;
                     const uint32_t K = wave_max_u32(key) - 1u;
-                    const int wi = (int)(K >> 13), wj = (int)(K & 8191u);
+                    const int wi = (int)(K >> KEY_JBITS), wj = (int)(K & KEY_JMASK);
                     const int wl = wj - wi + (qlen - 1) - dd0;           // lane that owns the winning diagonal
                     const int ws = __builtin_amdgcn_readlane(bS, wl);
                     const bool better = Mx > gM || (Mx == gM && (wi > gI || (wi == gI && wj > gJ)));
@@ -456,9 +467,9 @@ __global__ __launch_bounds__(NW * 64, MAXLEN == 320 ? 3 : (MAXLEN == 256 ? FAQCS
                 }
                 const int Mx = (int)wave_max_u32((uint32_t)(bM + 1)) - 1;
                 if (Mx >= 0) {
-                    const uint32_t key = (bM == Mx) ? ((((uint32_t)bI << 13) | (uint32_t)(bI + d)) + 1u) : 0u;
+                    const uint32_t key = (bM == Mx) ? ((((uint32_t)bI << KEY_JBITS) | (uint32_t)(bI + d)) + 1u) : 0u;
                     const uint32_t K = wave_max_u32(key) - 1u;
-                    const int wi = (int)(K >> 13), wj = (int)(K & 8191u);
+                    const int wi = (int)(K >> KEY_JBITS), wj = (int)(K & KEY_JMASK);
                     const int wl = wj - wi + (qlen - 1) - dd0;             // lane that owns the winning diagonal
                     const int ws = __builtin_amdgcn_readlane(bS, wl);
                     const bool better = Mx > gM || (Mx == gM && (wi > gI || (wi == gI && wj > gJ)));
@@ -467,10 +478,19 @@ __global__ __launch_bounds__(NW * 64, MAXLEN == 320 ? 3 : (MAXLEN == 256 ? FAQCS
             }
         };
 
+        // the reference's per-read state over the targets; target indices (best_j, last_j) are global: j0 + index in the group
+        const uint32_t j0 = GROUPED ? G.j0 : 0u;
         int best_score = 0, best_j = -1;
         bool have = false, known = false;
+        bool masked = false; // GROUPED: G.mask holds the read's mask (an earlier group masked part of it)
         uint32_t last_j = 0;
         int rs = 0, re = 0;
+        if (GROUPED) { // (one uniform 16-byte load: the state of read r, as the previous group's launch left it)
+            const uint4 s = G.state[r];
+            best_score = (int)(s.x & 0xffffu); best_j = (int)(s.x >> 16) - 1;
+            have = (s.y & 1u) != 0u; known = (s.y & 2u) != 0u; masked = (s.y & 4u) != 0u; last_j = s.y >> 16;
+            rs = (int)(s.z & 0xffffu); re = (int)(s.z >> 16);
+        }
         // ---- stage 1 for every adapter: two bits per adapter (any cell matches / the threshold is reachable) ---------
         uint64_t m_any = 0, m_pass = 0, m_bnd = 0; // m_bnd: stage 1 left the adapter's per-block bounds in s_sb
                                                    // (m_any, m_bnd: bit = adapter; m_pass: bit = the adapter's position in the class order)
@@ -489,7 +509,7 @@ __global__ __launch_bounds__(NW * 64, MAXLEN == 320 ? 3 : (MAXLEN == 256 ? FAQCS
             }
             // per-adapter scalars of this read, computed once with lane = adapter (n_adapters <= 64) and read back with v_readlane inside
             // the loop (the kernel is co-bound by scalar issue: what the loop does per adapter in scalar code is kept to a few unpacks):
-            //   va = |adapter| (14 bits) | first plane word << 14 (14) | plane words << 28
+            //   va = |adapter| (15 bits) | first plane word << 15
             //   vb = need_cnt (16) | coarse need << 16        vc = need + 32768 (16) | thr << 16
             // thr = the reference's threshold (trim.cpp:1007-1008 / :1082); need = 2 thr - min(|read|, |adapter|): what a block's best SCORE has
             // to reach ((mcap + score) / 2 >= thr); need_cnt = max(need, thr): what a diagonal's MATCH COUNT has to reach -- num_match =
@@ -507,7 +527,7 @@ __global__ __launch_bounds__(NW * 64, MAXLEN == 320 ? 3 : (MAXLEN == 256 ? FAQCS
                 const int need = 2 * th - (qlen < tl ? qlen : tl);
                 const int need_cnt = need > th ? need : th;
                 const int coarse = need_cnt - (tl > 32 ? tl - 32 : 0);
-                va = (uint32_t)tl | (me.y << 14);
+                va = (uint32_t)tl | (me.y << 15);
                 vb = (uint32_t)need_cnt | ((uint32_t)(coarse > 0 ? coarse : 0) << 16);
                 vc = (uint32_t)(need + 32768) | ((uint32_t)th << 16);
             }
@@ -519,11 +539,11 @@ __global__ __launch_bounds__(NW * 64, MAXLEN == 320 ? 3 : (MAXLEN == 256 ? FAQCS
             auto one = [&](const uint32_t l, auto nw_tag) {
                 constexpr int NWC = decltype(nw_tag)::value;
                 const uint32_t sa = (uint32_t)__builtin_amdgcn_readlane((int)va, (int)l), sb = (uint32_t)__builtin_amdgcn_readlane((int)vb, (int)l);
-                const int tlen = (int)(sa & 0x3fffu);
+                const int tlen = (int)(sa & 0x7fffu);
                 const int need_cnt = (int)(sb & 0xffffu);
                 bool may_pass = true;
                 if (NWC > 0 && prefilter_on) {
-                    const uint32_t *tpl = s_tpl + 4 * (sa >> 14);
+                    const uint32_t *tpl = s_tpl + 4 * (sa >> 15);
                     // (Measured and rejected: fetching the next adapter's first two plane words an adapter ahead, so that no LDS broadcast
                     // sits in front of its 20 dependent instructions: 128 VGPRs with a spill, 523 -> 470 M reads/s.)
                     // (Measured and rejected: leaving a last plane word of <= 3 bases uncompared and counting those bases as matches.
@@ -591,7 +611,7 @@ __global__ __launch_bounds__(NW * 64, MAXLEN == 320 ? 3 : (MAXLEN == 256 ? FAQCS
                     // per step.  Words 2u and 2u+1 face exactly the NBR+1 blocks u-1 .. u+NBR-1 (window index 2 NBR - 2i and
                     // 2 NBR + 1 - 2i for block u-1+i); block u-1 has seen all of its words after step u and leaves the accumulator.
                     constexpr int NACC = NBR + 1;
-                    const uint32_t *tpl = s_tpl + 4 * ((sa >> 14) & 0x3fffu);
+                    const uint32_t *tpl = s_tpl + 4 * (sa >> 15);
                     const int nw = (tlen + 31) >> 5;
                     const int nb = (qlen + tlen - 1 + 63) >> 6;
                     uint32_t cnt[NACC], maxcnt = 0;
@@ -649,8 +669,8 @@ __global__ __launch_bounds__(NW * 64, MAXLEN == 320 ? 3 : (MAXLEN == 256 ? FAQCS
             // class by class: inside a class the number of plane words is a compile-time constant (with the classes mixed in one loop the
             // compiler turns the choice into chains of scalar flag tests: 36 scalar instructions and 17 branches per adapter, measured)
             uint32_t l = 0;
-            const uint32_t e1 = uniu(s_ord[FAQCS_MAX_ADAPTERS + 1]), e2 = uniu(s_ord[FAQCS_MAX_ADAPTERS + 2]), e3 = uniu(s_ord[FAQCS_MAX_ADAPTERS + 3]),
-                           e4 = uniu(s_ord[FAQCS_MAX_ADAPTERS + 4]);
+            const uint32_t e1 = uniu(s_ord[FAQCS_ADAPTER_GROUP + 1]), e2 = uniu(s_ord[FAQCS_ADAPTER_GROUP + 2]), e3 = uniu(s_ord[FAQCS_ADAPTER_GROUP + 3]),
+                           e4 = uniu(s_ord[FAQCS_ADAPTER_GROUP + 4]);
 #pragma unroll 1
             for (; l < e1; ++l) one(l, std::integral_constant<int, 1>{});
 #pragma unroll 1
@@ -671,7 +691,19 @@ __global__ __launch_bounds__(NW * 64, MAXLEN == 320 ? 3 : (MAXLEN == 256 ? FAQCS
         // ---- stage 2 + the reference's sequential state (stale range, mask, credit), trim.cpp:1003-1071.  With every
         // adapter matching somewhere and none able to reach its threshold (the bulk of the reads) nothing can happen.
         const uint64_t m_all = A.n_adapters >= 64 ? ~0ull : ((1ull << A.n_adapters) - 1ull);
+        // GROUPED: the read's mask bytes mk[] from G.mask (or all unmasked when no group has masked the read yet)
+        auto load_mask = [&]() {
+#pragma unroll 1
+            for (int c = 0; c * 64 < qlen && c < (int)G.mask_words; ++c) {
+                const uint64_t w = masked ? G.mask[(size_t)r * G.mask_words + c] : ~0ull;
+                const int p = c * 64 + lane;
+                if (p < qlen) mk[p] = (uint8_t)((w >> lane) & 1ull);
+            }
+        };
+        bool in_stage2 = false; // (GROUPED) mk[] holds the read's mask
         if (!read_bad && qlen > 0 && !(m_pass == 0 && m_any == m_all)) {
+            in_stage2 = true;
+            bool dirty = false; // (GROUPED) this group masked part of the read
             // the per-base arrays of stage 2 are only needed here (a few percent of the reads)
             // (from the bytes this lane fetched for pack_query: a second global load here stalled every such read -- a fifth of them
             // with --polyA, whose weak threshold lets ~15 % of random reads through the prefilter -- for a memory latency)
@@ -684,6 +716,7 @@ __global__ __launch_bounds__(NW * 64, MAXLEN == 320 ? 3 : (MAXLEN == 256 ? FAQCS
                     if (p < qlen) { q[p] = s_na[cbyte[c]]; mk[p] = 1; }
                 }
             }
+            if (GROUPED && masked) load_mask();
             lds_sync_wave();
 #pragma unroll 1
             for (uint32_t j = 0; j < A.n_adapters; ++j) {
@@ -693,26 +726,50 @@ __global__ __launch_bounds__(NW * 64, MAXLEN == 320 ? 3 : (MAXLEN == 256 ? FAQCS
                 const bool any_match = (m_any >> j) & 1ull, may_pass = (m_pass >> uniu(s_pos[j])) & 1ull;
                 int score = 0;
                 if (any_match) {
-                    if (!may_pass) { have = true; known = false; last_j = j; continue; } // cannot mask, cannot be credited
+                    if (!may_pass) { have = true; known = false; last_j = j0 + j; continue; } // cannot mask, cannot be credited
                     int gM, gS, gI;
                     if ((m_bnd >> j) & 1ull) align_bits(j, gM, gS, gI); else align_exact(j, gM, gS, gI);
-                    if (gM >= 0) { have = true; known = true; last_j = j; rs = gS; re = gI; score = gM; }
+                    if (gM >= 0) { have = true; known = true; last_j = j0 + j; rs = gS; re = gI; score = gM; }
                     else if (!have) continue;                                // (only reachable with the prefilter disabled)
                 } else {
                     if (!have) continue;                                     // H2: unknown stale state -> no hit
-                    if (!known) { int gM, gS, gI; align_exact(last_j, gM, gS, gI); rs = gS; re = gI; known = true; }
+                    if (!known) {                                            // (GROUPED: last_j may belong to an earlier group)
+                        int gM, gS, gI;
+                        if (GROUPED && last_j < j0) align_exact(last_j, gM, gS, gI, true); else align_exact(last_j - j0, gM, gS, gI);
+                        rs = gS; re = gI; known = true;
+                    }
                 }
                 const int match_length = re - rs + 1;
                 const int num_match = (match_length + score) / 2;            // trim.cpp:1024-1025
                 if (num_match >= thr) {
                     for (int p = rs + lane; p <= re; p += 64) mk[p] = 0;     // trim.cpp:1032-1034
-                    if (score > best_score) { best_score = score; best_j = (int)j; }
+                    dirty = true;
+                    if (score > best_score) { best_score = score; best_j = (int)(j0 + j); } // strict >: an earlier target keeps a tie
                 }
             }
+            if (GROUPED && !G.last && dirty) { // the mask goes to the next group
+                lds_sync_wave();
+#pragma unroll 1
+                for (int c = 0; c * 64 < qlen && c < (int)G.mask_words; ++c) {
+                    const int p = c * 64 + lane;
+                    const uint64_t w = __ballot(p < qlen && mk[p] != 0);
+                    if (lane == 0) G.mask[(size_t)r * G.mask_words + c] = w;
+                }
+                masked = true;
+            }
+        } else if (GROUPED && !read_bad && qlen > 0) {
+            // the whole-group skip above: every target of the group set the stale state "have, not known" in turn
+            have = true; known = false; last_j = j0 + A.n_adapters - 1u;
         }
 
         uint32_t first = 0, second = (uint32_t)qlen;
-        if (best_score > 0) {
+        if (GROUPED && !G.last) {
+            if (lane == 0 && !read_bad && qlen > 0) // (a read with a bad base or no base never has state)
+                G.state[r] = make_uint4((uint32_t)best_score | ((uint32_t)(best_j + 1) << 16),
+                                        (have ? 1u : 0u) | (known ? 2u : 0u) | (masked ? 4u : 0u) | (last_j << 16),
+                                        (uint32_t)rs | ((uint32_t)re << 16), 0u);
+        } else if (best_score > 0) {
+            if (GROUPED && !in_stage2) load_mask(); // the last group did not reach stage 2: the mask of the earlier ones
             lds_sync_wave();
             // find_mask_range, trim.cpp:1144-1189, literal -- but walked run by run instead of base by base.  The loop's state
             // only changes where the mask changes: an unmasked run [s, e) adds e - s to run_length (setting run_start when it
@@ -746,17 +803,23 @@ __global__ __launch_bounds__(NW * 64, MAXLEN == 320 ? 3 : (MAXLEN == 256 ? FAQCS
             first = longest_run_length ? longest_run_start : 0u;
             second = longest_run_length;
             if (lane == 0) { // trim.cpp:1061-1064; block-local, one global atomic pair per adapter at the end of the block
-                atomicAdd(&s_ast[2 * best_j], 1u);
-                atomicAdd(&s_ast[2 * best_j + 1], (uint32_t)qlen - second);
+                if (GROUPED) { // (global index: straight to the counter block -- credited reads are rare)
+                    atomicAdd((unsigned long long *)&adapter_stats[2 * best_j], 1ull);
+                    atomicAdd((unsigned long long *)&adapter_stats[2 * best_j + 1], (unsigned long long)((uint32_t)qlen - second));
+                } else {
+                    atomicAdd(&s_ast[2 * best_j], 1u);
+                    atomicAdd(&s_ast[2 * best_j + 1], (uint32_t)qlen - second);
+                }
             }
         }
         // 0xffff = the read holds a base na_to_bits() rejects (seq_overlap.cpp:409): the trim kernel turns it into FAQCS_F_ERR_BASE
         if (lane == t) { res_sl = first | (second << 16); res_hit = read_bad ? 0xffffu : (uint32_t)(best_score > 0 ? best_j + 1 : 0); }
-        if (read_bad && lane == 0) atomicOr(err, 2u);
+        if (read_bad && lane == 0 && (!GROUPED || G.last)) atomicOr(err, 2u);
         lds_sync_wave();
       }
-      if (mine) { ad_sl[my] = res_sl; ad_hit[my] = (uint16_t)res_hit; }
+      if (mine && (!GROUPED || G.last)) { ad_sl[my] = res_sl; ad_hit[my] = (uint16_t)res_hit; }
     }
+    if (GROUPED) return;
     __syncthreads();
     for (uint32_t i = threadIdx.x; i < 2 * A.n_adapters; i += NW * 64)
         if (s_ast[i]) atomicAdd((unsigned long long *)&adapter_stats[i], (unsigned long long)s_ast[i]);
@@ -823,22 +886,22 @@ __global__ __launch_bounds__(NW * 64, 4) void adapter_overlap_pair(
 {
     constexpr int MAXLEN = 192;                // per-base arrays (reads of up to 160 bases; three 64-base pieces)
     constexpr int QW = MAXLEN / 32, PADL = 12, PW = QW + 2 * PADL;
-    constexpr int TPL_CAP = 4096;
+    constexpr int TPL_CAP = FAQCS_ADAPTER_TPL_CAP;
     constexpr int NBR = 9;                     // blocks of 32 diagonals: 160 + 128 - 1 <= 288
     constexpr int NCH = MAXLEN / 64;
     __shared__ uint8_t s_q[NW][2][MAXLEN];
     __shared__ uint8_t s_mask[NW][2][MAXLEN];
     __shared__ uint32_t s_pl[NW][2][4][PW];
     __shared__ __attribute__((aligned(16))) uint32_t s_tpl[TPL_CAP];
-    __shared__ uint8_t s_sb[NW][2][FAQCS_MAX_ADAPTERS][8]; // stage 1 -> stage 2: per 64-diagonal block, an upper bound of its best score
+    __shared__ uint8_t s_sb[NW][2][FAQCS_ADAPTER_GROUP][8]; // stage 1 -> stage 2: per 64-diagonal block, an upper bound of its best score
     __shared__ uint32_t s_bb[NW][136];
-    __shared__ uint32_t s_ast[2 * FAQCS_MAX_ADAPTERS];
+    __shared__ uint32_t s_ast[2 * FAQCS_ADAPTER_GROUP];
     __shared__ uint8_t s_iupac[32];
     __shared__ uint8_t s_na[256];
-    __shared__ uint32_t s_start[FAQCS_MAX_ADAPTERS + 1], s_wstart[FAQCS_MAX_ADAPTERS + 1];
-    __shared__ __attribute__((aligned(16))) uint4 s_meta[FAQCS_MAX_ADAPTERS];
-    __shared__ uint32_t s_pos[FAQCS_MAX_ADAPTERS];
-    __shared__ uint32_t s_ord[FAQCS_MAX_ADAPTERS + 8];
+    __shared__ uint32_t s_start[FAQCS_ADAPTER_GROUP + 1], s_wstart[FAQCS_ADAPTER_GROUP + 1];
+    __shared__ __attribute__((aligned(16))) uint4 s_meta[FAQCS_ADAPTER_GROUP];
+    __shared__ uint32_t s_pos[FAQCS_ADAPTER_GROUP];
+    __shared__ uint32_t s_ord[FAQCS_ADAPTER_GROUP + 8];
     const int lane = threadIdx.x & 63, half = lane >> 5, l32 = lane & 31;
     const int wave = uni(threadIdx.x >> 6);
     uint32_t *plw = &s_pl[wave][0][0][0];
@@ -849,7 +912,7 @@ __global__ __launch_bounds__(NW * 64, 4) void adapter_overlap_pair(
     const uint32_t tpl_dwords = 4u * A.wstart[A.n_adapters];
     for (uint32_t i = threadIdx.x; i < tpl_dwords; i += NW * 64) s_tpl[i] = A.planes[i]; // (the launcher has checked that they fit)
     if (threadIdx.x < 32) s_iupac[threadIdx.x] = threadIdx.x < 26 ? k_iupac[threadIdx.x] : (uint8_t)0;
-    for (uint32_t i = threadIdx.x; i < 2 * FAQCS_MAX_ADAPTERS; i += NW * 64) s_ast[i] = 0u;
+    for (uint32_t i = threadIdx.x; i < 2 * FAQCS_ADAPTER_GROUP; i += NW * 64) s_ast[i] = 0u;
     for (uint32_t i = threadIdx.x; i < A.n_adapters; i += NW * 64) {
         const uint32_t tl = A.start[i + 1] - A.start[i];
         uint32_t amask = 0;
@@ -868,7 +931,7 @@ __global__ __launch_bounds__(NW * 64, 4) void adapter_overlap_pair(
             const uint64_t m = __ballot(cls == c);
             if (cls == c) { const uint32_t at = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull)); s_ord[at] = (uint32_t)lane; s_pos[lane] = at; }
             base += (uint32_t)__popcll(m);
-            if (lane == 0) s_ord[FAQCS_MAX_ADAPTERS + c] = base; // end of class c
+            if (lane == 0) s_ord[FAQCS_ADAPTER_GROUP + c] = base; // end of class c
         }
     }
     __syncthreads();
@@ -1088,7 +1151,7 @@ __global__ __launch_bounds__(NW * 64, 4) void adapter_overlap_pair(
                 pass_v = (((uint32_t)lane == l && p0) || ((uint32_t)lane == l + 32u && p1)) ? 1u : pass_v;
             };
             uint32_t l = 0;
-            const uint32_t e1 = uniu(s_ord[FAQCS_MAX_ADAPTERS + 1]), e2 = uniu(s_ord[FAQCS_MAX_ADAPTERS + 2]), e3 = uniu(s_ord[FAQCS_MAX_ADAPTERS + 3]);
+            const uint32_t e1 = uniu(s_ord[FAQCS_ADAPTER_GROUP + 1]), e2 = uniu(s_ord[FAQCS_ADAPTER_GROUP + 2]), e3 = uniu(s_ord[FAQCS_ADAPTER_GROUP + 3]);
 #pragma unroll 1
             for (; l < e1; ++l) one(l, std::integral_constant<int, 1>{});
 #pragma unroll 1
@@ -1191,9 +1254,9 @@ __global__ __launch_bounds__(NW * 64, 4) void adapter_overlap_pair(
                     }
                     const int Mx = (int)wave_max_u32((uint32_t)(bM + 1)) - 1;
                     if (Mx >= 0) {
-                        const uint32_t key = (bM == Mx) ? ((((uint32_t)bI << 13) | (uint32_t)(bI + d)) + 1u) : 0u;
+                        const uint32_t key = (bM == Mx) ? ((((uint32_t)bI << KEY_JBITS) | (uint32_t)(bI + d)) + 1u) : 0u;
                         const uint32_t K = wave_max_u32(key) - 1u;
-                        const int wi = (int)(K >> 13), wj = (int)(K & 8191u);
+                        const int wi = (int)(K >> KEY_JBITS), wj = (int)(K & KEY_JMASK);
                         const int wl = wj - wi + (qlen - 1) - dd0;           // lane that owns the winning diagonal
                         const int ws = __builtin_amdgcn_readlane(bS, wl);
                         const bool better = Mx > gM || (Mx == gM && (wi > gI || (wi == gI && wj > gJ)));
@@ -1256,9 +1319,9 @@ __global__ __launch_bounds__(NW * 64, 4) void adapter_overlap_pair(
                     }
                     const int Mx = (int)wave_max_u32((uint32_t)(bM + 1)) - 1;
                     if (Mx >= 0) {
-                        const uint32_t key = (bM == Mx) ? ((((uint32_t)bI << 13) | (uint32_t)(bI + d)) + 1u) : 0u;
+                        const uint32_t key = (bM == Mx) ? ((((uint32_t)bI << KEY_JBITS) | (uint32_t)(bI + d)) + 1u) : 0u;
                         const uint32_t K = wave_max_u32(key) - 1u;
-                        const int wi = (int)(K >> 13), wj = (int)(K & 8191u);
+                        const int wi = (int)(K >> KEY_JBITS), wj = (int)(K & KEY_JMASK);
                         const int wl = wj - wi + (qlen - 1) - dd0;             // lane that owns the winning diagonal
                         const int ws = __builtin_amdgcn_readlane(bS, wl);
                         const bool better = Mx > gM || (Mx == gM && (wi > gI || (wi == gI && wj > gJ)));
@@ -1352,15 +1415,15 @@ __global__ __launch_bounds__(NW * 64, 4) void adapter_overlap_pair(
         if (s_ast[i]) atomicAdd((unsigned long long *)&adapter_stats[i], (unsigned long long)s_ast[i]);
 }
 
-hipError_t faqcs_launch_adapter(const AdapterDev &A, const uint8_t *seq, const uint32_t *off, uint32_t n_reads,
-                                uint32_t max_len, const uint32_t *seg_start, uint32_t n_segments, uint32_t *ad_sl,
-                                uint16_t *ad_hit, uint64_t *adapter_stats, uint32_t *err, uint32_t dbg, int n_cu, hipStream_t st)
+template <bool GROUPED>
+static hipError_t launch_adapter(const AdapterDev &A, const AdapterGroup &G, const uint8_t *seq, const uint32_t *off, uint32_t n_reads,
+                                 uint32_t max_len, const uint32_t *seg_start, uint32_t n_segments, uint32_t *ad_sl,
+                                 uint16_t *ad_hit, uint64_t *adapter_stats, uint32_t *err, uint32_t dbg, int n_cu, hipStream_t st)
 {
-    if (n_reads == 0) return hipSuccess;
     // two reads per wave (round 6): reads of up to 160 bases, at most 32 adapters of at most 128 bases whose planes fit the LDS copy;
-    // FAQCS_ADAPTER_PAIR=0 keeps adapter_overlap for them (A/B)
+    // FAQCS_ADAPTER_PAIR=0 keeps adapter_overlap for them (A/B).  (Not for a group of a larger library: the pair kernel carries no state.)
     static const bool pair_on = [] { const char *e = getenv("FAQCS_ADAPTER_PAIR"); return !e || atoi(e) != 0; }();
-    if (pair_on && max_len <= 160 && A.n_adapters <= 32 && A.longest <= 128 && A.plane_dwords <= 4096 && (dbg & 8u) == 0u) {
+    if (!GROUPED && pair_on && max_len <= 160 && A.n_adapters <= 32 && A.longest <= 128 && A.plane_dwords <= 4096 && (dbg & 8u) == 0u) {
         constexpr int NW = 4;
         uint32_t grid = (n_reads + 64 * NW - 1) / (64 * NW);
         const uint32_t cap = (uint32_t)n_cu * 8u;
@@ -1374,22 +1437,22 @@ hipError_t faqcs_launch_adapter(const AdapterDev &A, const uint8_t *seq, const u
         uint32_t grid = (n_reads + NW - 1) / NW;
         const uint32_t cap = (uint32_t)n_cu * 8u;
         if (grid > cap) grid = cap;
-        hipLaunchKernelGGL((adapter_overlap<NW, 256>), dim3(grid), dim3(NW * 64), 0, st, A, seq, off, n_reads, seg_start,
-                           n_segments, ad_sl, ad_hit, adapter_stats, err, dbg);
+        hipLaunchKernelGGL((adapter_overlap<NW, 256, GROUPED>), dim3(grid), dim3(NW * 64), 0, st, A, seq, off, n_reads, seg_start,
+                           n_segments, ad_sl, ad_hit, adapter_stats, err, dbg, G);
     } else if (max_len <= 320) { // MiSeq 2x300: the register-blocked prefilter with a 16-entry window per plane
         constexpr int NW = 4;
         uint32_t grid = (n_reads + NW - 1) / NW;
         const uint32_t cap = (uint32_t)n_cu * 6u;
         if (grid > cap) grid = cap;
-        hipLaunchKernelGGL((adapter_overlap<NW, 320>), dim3(grid), dim3(NW * 64), 0, st, A, seq, off, n_reads, seg_start,
-                           n_segments, ad_sl, ad_hit, adapter_stats, err, dbg);
+        hipLaunchKernelGGL((adapter_overlap<NW, 320, GROUPED>), dim3(grid), dim3(NW * 64), 0, st, A, seq, off, n_reads, seg_start,
+                           n_segments, ad_sl, ad_hit, adapter_stats, err, dbg, G);
     } else if (max_len <= 1024) {
         constexpr int NW = 8;
         uint32_t grid = (n_reads + NW - 1) / NW;
         const uint32_t cap = (uint32_t)n_cu * 4u;
         if (grid > cap) grid = cap;
-        hipLaunchKernelGGL((adapter_overlap<NW, 1024>), dim3(grid), dim3(NW * 64), 0, st, A, seq, off, n_reads, seg_start,
-                           n_segments, ad_sl, ad_hit, adapter_stats, err, dbg);
+        hipLaunchKernelGGL((adapter_overlap<NW, 1024, GROUPED>), dim3(grid), dim3(NW * 64), 0, st, A, seq, off, n_reads, seg_start,
+                           n_segments, ad_sl, ad_hit, adapter_stats, err, dbg, G);
     } else if (max_len <= FAQCS_MAX_READ_LENGTH) {
         // long reads: one wave per block, its LDS holds the per-base arrays of ONE read (2.5 bytes per base + 20 KB): the variant is picked by
         // the batch's longest read so that reads of a few thousand bases still get several waves per CU (5 / 4 / 2 / 1 blocks)
@@ -1398,8 +1461,8 @@ hipError_t faqcs_launch_adapter(const AdapterDev &A, const uint8_t *seq, const u
             uint32_t grid = n_reads;                                                                                               \
             const uint32_t cap = (uint32_t)n_cu * PER_CU;                                                                          \
             if (grid > cap) grid = cap;                                                                                            \
-            hipLaunchKernelGGL((adapter_overlap<1, ML>), dim3(grid), dim3(64), 0, st, A, seq, off, n_reads, seg_start, n_segments, \
-                               ad_sl, ad_hit, adapter_stats, err, dbg);                                                            \
+            hipLaunchKernelGGL((adapter_overlap<1, ML, GROUPED>), dim3(grid), dim3(64), 0, st, A, seq, off, n_reads, seg_start,    \
+                               n_segments, ad_sl, ad_hit, adapter_stats, err, dbg, G);                                             \
         }
         if (max_len <= 4096) FAQCS_ADAPTER_LONG(4096, 5u)
         else if (max_len <= 8192) FAQCS_ADAPTER_LONG(8192, 4u)
@@ -1410,4 +1473,17 @@ hipError_t faqcs_launch_adapter(const AdapterDev &A, const uint8_t *seq, const u
         return hipErrorInvalidValue;
     }
     return hipGetLastError();
+}
+
+// G == nullptr: the whole set in one pass (at most FAQCS_ADAPTER_GROUP targets of at most FAQCS_ADAPTER_SINGLE_LENGTH bases); else A is
+// one group of a larger library and G its place in the sequence of group launches (faqcs_capi.hip)
+hipError_t faqcs_launch_adapter(const AdapterDev &A, const AdapterGroup *G, const uint8_t *seq, const uint32_t *off, uint32_t n_reads,
+                                uint32_t max_len, const uint32_t *seg_start, uint32_t n_segments, uint32_t *ad_sl,
+                                uint16_t *ad_hit, uint64_t *adapter_stats, uint32_t *err, uint32_t dbg, int n_cu, hipStream_t st)
+{
+    if (n_reads == 0) return hipSuccess;
+    if (!G) return launch_adapter<false>(A, AdapterGroup{}, seq, off, n_reads, max_len, seg_start, n_segments, ad_sl, ad_hit, adapter_stats, err,
+                                         dbg, n_cu, st);
+    if (A.n_adapters == 0 || A.n_adapters > FAQCS_ADAPTER_GROUP || A.plane_dwords > FAQCS_ADAPTER_TPL_CAP) return hipErrorInvalidValue;
+    return launch_adapter<true>(A, *G, seq, off, n_reads, max_len, seg_start, n_segments, ad_sl, ad_hit, adapter_stats, err, dbg, n_cu, st);
 }

@@ -40,7 +40,7 @@ hipError_t faqcs_launch_trim(const DevParams &P, const uint8_t *seq, const uint8
 hipError_t faqcs_launch_terminal_n_flags(const uint8_t *seq, const uint32_t *off, uint32_t n_reads, uint8_t *flags, hipStream_t st);
 hipError_t faqcs_launch_composition(const unsigned long long *rec_pre, const unsigned long long *rec_post, uint32_t n, bool wide,
                                     const float *comp_norm, uint64_t *dst_pre, uint64_t *dst_post, int n_cu, hipStream_t st);
-hipError_t faqcs_launch_adapter(const AdapterDev &A, const uint8_t *seq, const uint32_t *off, uint32_t n_reads,
+hipError_t faqcs_launch_adapter(const AdapterDev &A, const AdapterGroup *G, const uint8_t *seq, const uint32_t *off, uint32_t n_reads,
                                 uint32_t max_len, const uint32_t *seg_start, uint32_t n_segments, uint32_t *ad_sl,
                                 uint16_t *ad_hit, uint64_t *adapter_stats, uint32_t *err, uint32_t dbg, int n_cu, hipStream_t st);
 hipError_t faqcs_launch_synth(uint8_t *d_seq, uint8_t *d_qual, uint32_t *d_offset, uint32_t n_reads, uint32_t L,
@@ -99,6 +99,13 @@ struct faqcs_ctx {
     uint32_t *d_astart = nullptr, *d_aplanes = nullptr, *d_awstart = nullptr;
     float match_rate = 0.f;
     uint32_t adapter_longest = 0, adapter_plane_dwords = 0;
+    // a library of more than FAQCS_ADAPTER_GROUP targets, or with a target of more than FAQCS_ADAPTER_SINGLE_LENGTH bases: consecutive groups
+    // of targets, one adapter_overlap launch each, that carry every read's state in s_astate / s_amask (faqcs_dev.h); empty: one pass
+    struct AdapterGroupHost { uint32_t j0, n, w0, longest, plane_dwords; };
+    std::vector<AdapterGroupHost> agroups;
+    uint32_t *d_awstart_grp = nullptr; // per group g, n + 1 word offsets rebased to the group's first plane word, from d_awstart_grp + j0 + g
+    DevBuf<uint4> s_astate;
+    DevBuf<uint64_t> s_amask;
     // staging for host submissions: two input slots so the H2D copy of batch k+1 overlaps the kernels of batch k
     struct Slot { DevBuf<uint8_t> seq, qual, tn; DevBuf<uint32_t> off; hipEvent_t done = nullptr; bool used = false; };
     Slot slot[2];
@@ -336,7 +343,8 @@ extern "C" int faqcs_create(const faqcs_params *p, int device_id, faqcs_ctx **ou
     if (!p || !out) return fail(FAQCS_E_INVAL, "faqcs_create: null argument");
     if (p->abi_version != FAQCS_ABI_VERSION) return fail(FAQCS_E_INVAL, "faqcs_create: ABI version mismatch");
     if (p->max_read_length == 0 || p->max_read_length > FAQCS_MAX_READ_LENGTH) return fail(FAQCS_E_INVAL, "faqcs_create: max_read_length out of range");
-    if (p->n_adapters > FAQCS_MAX_ADAPTERS) return fail(FAQCS_E_INVAL, "faqcs_create: too many adapters");
+    if (p->n_adapters > FAQCS_MAX_ADAPTERS)
+        return fail(FAQCS_E_INVAL, "faqcs_create: " + std::to_string(p->n_adapters) + " adapters, at most " + std::to_string(FAQCS_MAX_ADAPTERS) + " are supported");
     if (p->mode < 0 || p->mode > 2) return fail(FAQCS_E_INVAL, "trim.cpp:trim_read: Undefined trimming mode!");
     // the argmax keys of the trim kernel hold |sum of (Q - q)| <= 1024 * (|Q| + 41) in 18 bits (16 for reads <= 256 bases)
     if (p->quality < -93 || p->quality > 93) return fail(FAQCS_E_INVAL, "faqcs_create: quality threshold outside [-93, 93]");
@@ -383,7 +391,9 @@ extern "C" int faqcs_create(const faqcs_params *p, int device_id, faqcs_ctx **ou
         for (uint32_t j = 0; j < p->n_adapters; ++j) {
             const char *s = p->adapter_seq[j];
             const size_t L = strlen(s);
-            if (L == 0 || L > FAQCS_MAX_ADAPTER_LENGTH) return fail(FAQCS_E_INVAL, "faqcs_create: adapter length out of range");
+            if (L == 0 || L > FAQCS_MAX_ADAPTER_LENGTH)
+                return fail(FAQCS_E_INVAL, "faqcs_create: adapter " + std::to_string(j) + " has " + std::to_string(L) + " bases, 1 ... " +
+                                               std::to_string(FAQCS_MAX_ADAPTER_LENGTH) + " are supported");
             c->adapters.emplace_back(s);
             for (size_t k = 0; k < L; ++k) {
                 const uint8_t b = na_to_bits_host(s[k]);
@@ -409,6 +419,22 @@ extern "C" int faqcs_create(const faqcs_params *p, int device_id, faqcs_ctx **ou
         c->adapter_plane_dwords = (uint32_t)planes.size();
         for (uint32_t j = 0; j < p->n_adapters; ++j) c->adapter_longest = std::max(c->adapter_longest, start[j + 1] - start[j]);
         c->match_rate = (float)(1.0 - (double)p->filterAdapterMismatchRate); // trim.cpp:969
+        if (p->n_adapters > FAQCS_ADAPTER_GROUP || c->adapter_longest > FAQCS_ADAPTER_SINGLE_LENGTH) {
+            // consecutive groups of at most FAQCS_ADAPTER_GROUP targets whose planes fit the kernel's LDS copy (a target of 32 767 bases
+            // has 1 024 plane words = FAQCS_ADAPTER_TPL_CAP dwords: every target fits a group of its own)
+            std::vector<uint32_t> wgrp;
+            for (uint32_t j = 0; j < p->n_adapters;) {
+                faqcs_ctx::AdapterGroupHost g{j, 0, wstart[j], 0, 0};
+                while (j < p->n_adapters && g.n < FAQCS_ADAPTER_GROUP && 4u * (wstart[j + 1] - g.w0) <= FAQCS_ADAPTER_TPL_CAP) {
+                    g.longest = std::max(g.longest, start[j + 1] - start[j]);
+                    ++g.n; ++j;
+                }
+                g.plane_dwords = 4u * (wstart[j] - g.w0);
+                for (uint32_t k = g.j0; k <= j; ++k) wgrp.push_back(wstart[k] - g.w0);
+                c->agroups.push_back(g);
+            }
+            HIPCHK(upload(&c->d_awstart_grp, wgrp));
+        }
     }
 
     DevParams &d = c->dp;
@@ -476,11 +502,11 @@ extern "C" void faqcs_destroy(faqcs_ctx *c)
     if (c->ins_b) (void)hipEventDestroy(c->ins_b);
     for (int k = 0; k < 2; ++k) { if (c->fwd_free[k]) (void)hipEventDestroy(c->fwd_free[k]); if (c->fwd_copied[k]) (void)hipEventDestroy(c->fwd_copied[k]); c->fwd_items[k].release(); }
     void *ptrs[] = {c->d_lcthr, c->d_basetab, c->d_avgq, c->d_norm, c->d_magic, c->d_counters, c->d_err, c->d_partials, c->d_abits, c->d_astart, c->d_aplanes, c->d_awstart,
-                    c->kt.slots, c->kt.stats, c->kt.dirty, c->d_fold_claim, c->d_snaps, c->d_ob, c->d_tot_by_epoch, c->d_first_hist};
+                    c->d_awstart_grp, c->kt.slots, c->kt.stats, c->kt.dirty, c->d_fold_claim, c->d_snaps, c->d_ob, c->d_tot_by_epoch, c->d_first_hist};
     for (void *q : ptrs) if (q) (void)hipFree(q);
     for (auto &sl : c->slot) { sl.seq.release(); sl.qual.release(); sl.tn.release(); sl.off.release(); if (sl.done) (void)hipEventDestroy(sl.done); }
     for (auto &e : c->ticket_ev) if (e) (void)hipEventDestroy(e);
-    c->s_seg.release(); c->s_sl.release(); c->s_hit.release(); c->s_res.release();
+    c->s_seg.release(); c->s_sl.release(); c->s_hit.release(); c->s_res.release(); c->s_astate.release(); c->s_amask.release();
     for (auto &rs : c->rec) { rs.pre.release(); rs.post.release(); if (rs.trimmed) (void)hipEventDestroy(rs.trimmed); if (rs.folded) (void)hipEventDestroy(rs.folded); }
     if (c->aux) (void)hipStreamDestroy(c->aux);
     c->ob_items.release(); c->ob_wave_count.release(); c->ob_wave_offset.release();
@@ -905,9 +931,25 @@ static int enqueue(faqcs_ctx *c, const uint8_t *d_seq, const uint8_t *d_qual, co
         HIPCHK(c->s_sl.reserve(n)); HIPCHK(c->s_hit.reserve(n)); HIPCHK(c->s_seg.reserve(n_seg + 1));
         d_sl = c->s_sl.p; d_hit = c->s_hit.p;
         HIPCHK(hipMemcpyAsync(c->s_seg.p, seg, (n_seg + 1) * 4, hipMemcpyHostToDevice, c->compute));
-        AdapterDev A{c->d_abits, c->d_astart, c->d_aplanes, c->d_awstart, p.n_adapters, c->match_rate, c->adapter_longest, c->adapter_plane_dwords};
-        HIPCHK(faqcs_launch_adapter(A, d_seq, d_off, n, max_len, c->s_seg.p, n_seg, d_sl, d_hit,
-                                    c->d_counters + c->lay.adapter_stats, c->d_err, c->dp.dbg, c->n_cu, c->compute));
+        if (c->agroups.empty()) {
+            AdapterDev A{c->d_abits, c->d_astart, c->d_aplanes, c->d_awstart, p.n_adapters, c->match_rate, c->adapter_longest, c->adapter_plane_dwords};
+            HIPCHK(faqcs_launch_adapter(A, nullptr, d_seq, d_off, n, max_len, c->s_seg.p, n_seg, d_sl, d_hit,
+                                        c->d_counters + c->lay.adapter_stats, c->d_err, c->dp.dbg, c->n_cu, c->compute));
+        } else { // one launch per group of targets, in library order; every read's state is carried from one to the next
+            AdapterGroup G{};
+            G.mask_words = (max_len + 63) / 64;
+            HIPCHK(c->s_astate.reserve(n)); HIPCHK(c->s_amask.reserve((size_t)n * G.mask_words));
+            HIPCHK(hipMemsetAsync(c->s_astate.p, 0, (size_t)n * sizeof(uint4), c->compute));
+            G.state = c->s_astate.p; G.mask = c->s_amask.p; G.gstart = c->d_astart;
+            for (size_t k = 0; k < c->agroups.size(); ++k) {
+                const faqcs_ctx::AdapterGroupHost &g = c->agroups[k];
+                AdapterDev A{c->d_abits, c->d_astart + g.j0, c->d_aplanes + 4 * (size_t)g.w0, c->d_awstart_grp + g.j0 + k, g.n, c->match_rate,
+                             g.longest, g.plane_dwords};
+                G.j0 = g.j0; G.last = k + 1 == c->agroups.size() ? 1u : 0u;
+                HIPCHK(faqcs_launch_adapter(A, &G, d_seq, d_off, n, max_len, c->s_seg.p, n_seg, d_sl, d_hit,
+                                            c->d_counters + c->lay.adapter_stats, c->d_err, c->dp.dbg, c->n_cu, c->compute));
+            }
+        }
     }
     if (n) {
         Timing &t = *tm;

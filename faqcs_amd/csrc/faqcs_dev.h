@@ -51,6 +51,27 @@ struct DevParams {
     uint64_t *fold_dst_pre, *fold_dst_post;
 };
 
+// The adapter pre-pass (faqcs_adapter_kernel.hip) holds one GROUP of targets in LDS: at most FAQCS_ADAPTER_GROUP targets (one per lane of
+// a wave) whose bit-planes fit its FAQCS_ADAPTER_TPL_CAP-dword copy.  A set of at most FAQCS_ADAPTER_GROUP targets of at most
+// FAQCS_ADAPTER_SINGLE_LENGTH bases runs in one pass; a larger library (up to FAQCS_MAX_ADAPTERS targets of up to FAQCS_MAX_ADAPTER_LENGTH
+// bases) is cut into consecutive groups, one launch per group, that carry each read's state (AdapterGroup) from one launch to the next.
+#define FAQCS_ADAPTER_GROUP 64
+#define FAQCS_ADAPTER_TPL_CAP 4096
+#define FAQCS_ADAPTER_SINGLE_LENGTH 8192
+
+// The state of trim_adapters_and_phiX's loop over the targets (trim.cpp:1003-1071) for one read, between two group launches:
+//   x = best_score | (1 + best_j) << 16     (best_j: global index of the credited target, -1 = none)
+//   y = have | known << 1 | masked << 2 | last_j << 16   (the H2 stale range of target last_j, global index; masked: `mask` holds the read's mask)
+//   z = rs | re << 16                       (the stale range, valid when known)
+struct AdapterGroup {
+    uint4 *state;           // [n_reads], zero before the first group
+    uint64_t *mask;         // [n_reads][mask_words]: bit p of word c = position 64 c + p is unmasked (written once a group masks the read)
+    const uint32_t *gstart; // [n_all + 1] base offsets of every target of the library into AdapterDev::bits
+    uint32_t j0;            // global index of the group's first target
+    uint32_t mask_words;    // 64-base words per read (>= ceil(longest read / 64))
+    uint32_t last;          // the last group: find_mask_range, credit, ad_sl / ad_hit / err
+};
+
 enum { FS_SLOTS = 32 };
 enum { FAQCS_PARTIAL_ROW = 16896 };  // >= N_ZERO of every trim_lds variant (RowCfg<19, 8, 160>: 7 962, <16, 16, 288>: 13 792, <19, 16, 352>: 16 768): dwords of one flushed copy of a block's LDS accumulators
 enum { FAQCS_PARTIAL_FLUSHES = 8 };  // flushes (rows) a block has room for in one launch: it stops claiming chunks before it would need more

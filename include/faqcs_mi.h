@@ -55,8 +55,12 @@ enum {
                                        adapter_overlap<1, 32768> (one wave per read) */
 #define FAQCS_ARENA_PAD_BEFORE 16 /* readable bytes required in front of / behind a batch's arenas (faqcs_batch) */
 #define FAQCS_ARENA_PAD_AFTER 64
-#define FAQCS_MAX_ADAPTERS 64
-#define FAQCS_MAX_ADAPTER_LENGTH 8192
+/* Adapter / contaminant library (faqcs_params.adapter_seq): up to 65 534 targets -- faqcs_read_result.adapter holds 1 + index in 16 bits
+   and 0xffff marks a bad base -- of up to 32 767 bases each (the reference's aligner scores in int16, seq_overlap.h:80).  faqcs_create()
+   refuses anything larger with FAQCS_E_INVAL; nothing is truncated.  Sets of at most 64 targets of at most 8 192 bases run in one pass of
+   the pre-pass; larger ones in consecutive groups of targets. */
+#define FAQCS_MAX_ADAPTERS 65534
+#define FAQCS_MAX_ADAPTER_LENGTH 32767
 
 enum { FAQCS_MODE_HARD = 0, FAQCS_MODE_BWA = 1, FAQCS_MODE_BWA_PLUS = 2 }; /* Options::Mode, FaQCs.h:90-95 */
 
@@ -342,7 +346,7 @@ int  faqcs_debug_words(faqcs_ctx *ctx, uint64_t *out, uint32_t n);
  * HIP events recorded on the compute stream around each launch */
 int  faqcs_kernel_time_ms(faqcs_ctx *ctx, double *avg_ms, uint64_t *n_launches);
 /* the same per kernel: the trim kernel (and which variant ran: "trim_lds", "trim_tpr", "trim_filter_accumulate") and the
- * adapter pre-pass adapter_overlap (0 without adapters); both measured with HIP events on the compute stream */
+ * adapter pre-pass adapter_overlap (0 without adapters; a library of several target groups: all its launches); both measured with HIP events on the compute stream */
 typedef struct faqcs_kernel_times {
     double trim_ms, adapter_ms; uint64_t n_launches; const char *trim_kernel;
     double kmer_ms;        /* k-mer kernels of a submission (kmer_count; kmer_extract in the owner-partitioned mode), per submission */
