@@ -125,11 +125,9 @@ __device__ __forceinline__ int wave_sum_i32(int v) { return __builtin_amdgcn_rea
 __device__ __forceinline__ int op_add_(int a, int b) { return a + b; }
 __device__ __forceinline__ int op_or_(int a, int b) { return a | b; }
 __device__ __forceinline__ int op_umax_(int a, int b) { return (int)umax_((uint32_t)a, (uint32_t)b); }
-__device__ __forceinline__ int op_imax_(int a, int b) { return a > b ? a : b; }
 __device__ __forceinline__ int row_all_sum(int v) { FAQCS_ROW_ALL(op_add_) return v; }
 __device__ __forceinline__ uint32_t row_all_or(uint32_t x) { int v = (int)x; FAQCS_ROW_ALL(op_or_) return (uint32_t)v; }
 __device__ __forceinline__ uint32_t row_all_umax(uint32_t x) { int v = (int)x; FAQCS_ROW_ALL(op_umax_) return (uint32_t)v; }
-__device__ __forceinline__ int row_all_imax(int v) { FAQCS_ROW_ALL(op_imax_) return v; }
 // inclusive prefix sum inside each row of 16 lanes
 __device__ __forceinline__ int row_incl_scan_add(int v)
 {

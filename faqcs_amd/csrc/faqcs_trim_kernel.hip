@@ -1,20 +1,21 @@
-// faqcs_trim_kernel.hip -- trim_tpr, trim_filter_accumulate + composition_histogram (gfx950, wave64).
+// faqcs_trim_kernel.hip -- trim_filter_accumulate, composition_histogram and the trim dispatcher (gfx950, wave64).
 //
 // Replaces trim_read() and its helpers (trim.cpp:225-551, :553-597, :629-885, :1191-1216) for every read
-// of a batch.  Three kernels share the accumulators, the flush and the per-chunk epilogue (faqcs_trim_common.h);
-// faqcs_launch_trim at the end of this file picks one per submission:
-//   trim_lds (faqcs_trim_lds_kernel.hip)   reads of 77 ... 304 bases, every option set but --replace_to_N_q: the headline shapes
-//   trim_tpr                 the default-like option sets on reads of up to 76 bases: two phases per 64-read chunk, described at
-//                            its definition (its wider instantiations are kept for A/B runs: FAQCS_TRIM_LDS=0)
-//   trim_filter_accumulate   every other option set and read length up to 1 024 bases: one pass, described here
+// of a batch.  Two kernels live in this file: trim_filter_accumulate (the single-pass trim kernel) and composition_histogram
+// (folds the per-read composition records).  The trim kernels of the library share the accumulators, the flush and the per-chunk
+// epilogue (faqcs_trim_common.h); faqcs_launch_trim at the end of this file picks one per submission by the longest read of the batch:
+//   trim_lds (faqcs_trim_lds_kernel.hip)    1 ... 304 bases, every option set but --replace_to_N_q and the FAQCS_DBG ablation bits
+//   trim_filter_accumulate                  everything else up to 1 024 bases (--replace_to_N_q, FAQCS_DBG, 305 ... 1 024 bases, and
+//                                           what FAQCS_TRIM_LDS=0 / FAQCS_TRIM_LDS4=0 / FAQCS_TRIM_LDS16=0 take from trim_lds): described here
+//   trim_long (faqcs_trim_long_kernel.hip)  a batch that holds a read of more than 1 024 bases (FAQCS_TRIM_LONG=1: every batch)
 //
 // Mapping (trim_filter_accumulate).  LPR lanes share one read and lane l of the group owns the C consecutive positions [l*C, l*C+C), fetched
 // with ONE unaligned global_load_dwordx{D} per arena; a wave takes chunks of 64 reads.
-//   LPR =  4  reads <= 76 bases (C = 16 / 19):      sixteen reads per wave, one per DPP quad
-//   LPR =  8  reads <= 160 bases (C = 8 ... 20):    eight reads per wave, two per 16-lane DPP row
-//   LPR = 16  reads <= 256 bases (C = 4 ... 16):    four reads per wave, one per DPP row
-//   LPR = 32  reads <= 512 bases (C = 10 / 16):     two reads per wave
-//   LPR = 64  reads <= 1024 bases (C = 16; 5 / 8 as the A/B fallback of LPR = 32): the whole wave on one read
+//   LPR =  4  reads <= 76 bases (C = 16 / 19):        sixteen reads per wave, one per DPP quad
+//   LPR =  8  reads <= 160 bases (C = 13 ... 20):     eight reads per wave, two per 16-lane DPP row
+//   LPR = 16  reads <= 256 bases (C = 13 / 16):       four reads per wave, one per DPP row
+//   LPR = 32  reads <= 512 bases (C = 10 / 16):       two reads per wave
+//   LPR = 64  reads <= 1024 bases (C = 12 / 16):      the whole wave on one read
 // Every per-read scalar (length, window, cut points, filter decision) is a group-uniform VGPR value: there are no
 // ballots and no scalar-ALU bit logic in the loop (round-1 profiling showed the ballot formulation was SALU-bound at
 // ~900 scalar instructions per read).  Cross-lane work is DPP only (RowOps<LPR> in faqcs_dev.h): prefix scans and
@@ -46,16 +47,6 @@
 #ifndef FAQCS_TRIM_NW
 #define FAQCS_TRIM_NW 4        /* waves per block (A/B on MI355X: 4 waves x 3 blocks/CU beat 8 x 1 by 9 %) */
 #endif
-// trim_tpr: ONE block per CU (its LDS holds 10 KB of prefix snapshots per wave): 12 waves = 3 per SIMD while the registers
-// allow it (C = 19, the 2x150 shape: 168 VGPRs without a spill), 8 waves otherwise
-constexpr int tpr_waves_per_simd(int C, int LPR = 8, bool ext = false) { return (LPR == 4 || (C == 19 && !ext) || C == 13) ? 3 : 2; } // what the hardware gets to run
-// C = 19: one block of 12 waves, compiled for 3 waves per SIMD (168 VGPRs, no spill).  C = 13 needs 152 registers when the
-// compiler is asked for 2 waves per SIMD but spills under a 168 cap, so it is compiled for 2 and launched as three
-// blocks of 4 waves (the hardware co-schedules them: 152 <= 168).  C = 20: one block of 8.
-// 4 lanes per read in phase B (reads <= 76 bases): like C = 13.
-// EXT (--5trim_off, --avg_q, -n 0/1 on top of the default set): C = 19 then runs one block of 8 like C = 20.
-constexpr int tpr_nw(int C, int LPR = 8, bool ext = false) { return LPR == 4 ? 4 : (C == 19 ? (ext ? 8 : 12) : (C == 13 ? 4 : 8)); }
-constexpr int tpr_bounds_waves(int C, int LPR = 8, bool ext = false) { return (LPR == 8 && C == 19 && !ext) ? 3 : 2; }
 #ifndef FAQCS_TRIM_MINWAVES
 #define FAQCS_TRIM_MINWAVES 3  /* __launch_bounds__ 2nd argument: waves per SIMD the register allocator must allow */
 #endif
@@ -612,633 +603,6 @@ __global__ __launch_bounds__(NW * 64, (LPR == 8 || C > 10) ? 2 : FAQCS_TRIM_MINW
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// trim_tpr: the headline option set (BWA_plus, 5' trimming on, -n 2, no --qc_only / --replace_to_N_q / --avg_q)
-// for reads of at most 160 bases, in two phases per 64-read chunk.
-//
-//   phase A, "thread per read": the lane that OWNS a read holds its bytes in registers (ten 16-byte loads per
-//     arena) and takes every per-read decision alone: class counts (an LDS table with 8-bit A,T,C,G fields, a prefix
-//     snapshot per dword parked in LDS), upper-case N bits, quality sum and range check on four bytes per
-//     instruction, the two BWA_plus walks exactly as trim.cpp:714-793 states them (serially, position by position,
-//     all 64 reads in lockstep; a dword no lane still needs is skipped), length / poly-N / low-complexity filters.
-//     No cross-lane reduction and no row-uniform control flow is left: what used to be ~300 instructions per 8 reads
-//     is now spent once per 64.
-//   phase B, position-parallel (8 lanes per read, as trim_filter_accumulate): only applies the window -- position x
-//     quality and position x base accumulation.
-//   Rare inputs (a raw quality outside [offset, offset + 41], letters other than ACGTN, dinucleotide candidates)
-//     take exact per-position passes over the registers, entered only by chunks that contain such a read.
-// ---------------------------------------------------------------------------------------------------------
-template <int C, int LPR = 8> struct TprCfg {
-    using Row = RowCfg<C, LPR>;
-    static constexpr int NP = (Row::W + 15) / 16;  // 16-byte pieces per read and arena (the out-of-line exact passes)
-    static constexpr int ND = (Row::W + 3) / 4;    // dwords per read and arena held by the owner lane
-    static constexpr int NF = ND / 4, NR = ND % 4; // ... fetched as NF 16-byte pieces and one of NR dwords
-    static constexpr int SROW = 65;                // dwords per snapshot row: 64 lanes + 1, so that a column walk changes bank
-    static constexpr int NWORD = (ND * 4 + 31) / 32;
-    static constexpr int O_T2 = (Row::LDS_DWORDS + 3) & ~3;   // [256][2]: A,T,C,G one-hot in 8-bit fields ; isN(upper) | isN(any) << 1
-    static constexpr int O_SNAP = O_T2 + 512;                 // [NW][ND][SROW] class counts before dword k; after phase A: the qualities
-    static constexpr int SNAP_WAVE = ND * SROW;
-    static constexpr int lds_dwords(int nw) { return O_SNAP + nw * SNAP_WAVE; }
-};
-
-namespace {
-constexpr int TPR_SROW_BYTES = 65 * 4; // == TprCfg::SROW * 4
-typedef uint32_t LdsPair __attribute__((ext_vector_type(2)));
-typedef const __attribute__((address_space(3))) LdsPair *lds_u2_ptr;
-__device__ __forceinline__ void lds_store_u32(uint32_t byte_offset, uint32_t v) { *(lds_u32_mut)(size_t)byte_offset = v; }
-__device__ __forceinline__ uint32_t lds_load_u32(uint32_t byte_offset) { return *(lds_u32_ptr)(size_t)byte_offset; }
-template <int K> __device__ __forceinline__ uint32_t byte_times8(uint32_t w, uint32_t three)
-{
-    uint32_t r;
-    if (K == 0) asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0" : "=v"(r) : "v"(three), "v"(w));
-    else if (K == 1) asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1" : "=v"(r) : "v"(three), "v"(w));
-    else if (K == 2) asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2" : "=v"(r) : "v"(three), "v"(w));
-    else asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_3" : "=v"(r) : "v"(three), "v"(w));
-    return r;
-}
-// mask of the bytes [0, nb) of a dword, nb in 0..4
-__device__ __forceinline__ uint32_t low_bytes(int nb) { return nb >= 4 ? 0xffffffffu : ((1u << (8 * nb)) - 1u); }
-// bits [s, e) of a 32-bit word, 0 <= s, e <= 32
-__device__ __forceinline__ uint32_t bit_range(int s, int e)
-{
-    const uint32_t hi = e >= 32 ? 0xffffffffu : ((1u << e) - 1u), lo = s >= 32 ? 0xffffffffu : ((1u << s) - 1u);
-    return hi & ~lo;
-}
-} // namespace
-
-// ---- exact per-position passes of phase A, entered only by a chunk that holds such a read.  Out of line on purpose: their
-// register needs must not weigh on the main path (a call saves what it clobbers only when it is taken).
-struct ExactQuality { int sv, svp, mq; };   // sum(raw - offset) over the read / over the kept window, max(raw - offset)
-// patch = lead | trail << 8: terminal-N positions (< lead or >= trail) read as the offset (mask_quality_terminal_N)
-template <int NP>
-__device__ __noinline__ ExactQuality exact_quality_pass(const uint8_t *__restrict__ qual, const uint32_t v_off, const int len, const uint32_t patch,
-                                                        const int a, const int n, const int in_off)
-{
-    const int lead = (int)(patch & 0xffu), trail = (int)(patch >> 8);
-    ExactQuality r{0, 0, 0};
-#pragma unroll 1
-    for (int k = 0; k < NP; ++k) {
-        if (!__any(16 * k < len)) break;
-        PackedBytes<4> tq;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) tq.w[i] = 0u;
-        if (16 * k < len) tq = *(const PackedBytes<4> *)(qual + (size_t)v_off + 16 * k);
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int p = 16 * k + i;
-            int v = (int)(int8_t)((tq.w[i >> 2] >> (8 * (i & 3))) & 0xffu) - in_off;
-            if (p < lead || p >= trail) v = 0;
-            if (p < len) {
-                r.sv += v;
-                r.mq = r.mq > v ? r.mq : v;
-                if ((unsigned)(p - a) < (unsigned)n) r.svp += v;
-            }
-        }
-    }
-    return r;
-}
-struct ExactBases { uint32_t npre, npost; bool trip; }; // N (any case) in the read / in the kept window; dinucleotide filter
-template <int NP>
-__device__ __noinline__ ExactBases exact_base_pass(const uint8_t *__restrict__ seq, const uint32_t v_off, const int len, const int a, const int n,
-                                                   const bool dinuc, const uint32_t dthr, const uint32_t cpk, const uint32_t snap_base,
-                                                   const uint32_t t2_lds)
-{
-    ExactBases r{0u, 0u, false};
-    uint32_t prev = 8u; // class 0..3 of the previous position if it is ACGT inside the window
-    // (the lane's snapshot column is free by now and holds the 16 transition counters)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) lds_store_u32(snap_base + (uint32_t)i * (uint32_t)(TPR_SROW_BYTES), 0u);
-#pragma unroll 1
-    for (int k = 0; k < NP; ++k) {
-        if (!__any(16 * k < len)) break;
-        PackedBytes<4> ts;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) ts.w[i] = 0u;
-        if (16 * k < len) ts = *(const PackedBytes<4> *)(seq + (size_t)v_off + 16 * k);
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int p = 16 * k + i;
-            const uint32_t byte = p < len ? (ts.w[i >> 2] >> (8 * (i & 3))) & 0xffu : 0u;
-            const LdsPair e = *(lds_u2_ptr)(size_t)(byte * 8u + t2_lds);
-            const bool inw = (unsigned)(p - a) < (unsigned)n;
-            const uint32_t isn = (e.y >> 1) & 1u;
-            r.npre += isn;
-            r.npost += inw ? isn : 0u;
-            const uint32_t cur = (e.x != 0u && inw) ? (uint32_t)__builtin_ctz(e.x) >> 3 : 8u;
-            if (dinuc && cur < 4u && prev < 4u && cur != prev)
-                __hip_atomic_fetch_add((lds_u32_mut)(size_t)(snap_base + (prev * 4u + cur) * (uint32_t)(TPR_SROW_BYTES)), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            prev = cur;
-        }
-    }
-    if (dinuc) { // dc[X->Y] <= min(count X, count Y): only pairs whose two counts both reach dthr can trip
-#pragma unroll
-        for (int x = 0; x < 4; ++x)
-#pragma unroll
-            for (int y = 0; y < 4; ++y)
-                if (x != y) {
-                    const uint32_t dc = lds_load_u32(snap_base + (uint32_t)(x * 4 + y) * (uint32_t)(TPR_SROW_BYTES));
-                    r.trip = r.trip || (((cpk >> (8 * x)) & 0xffu) >= dthr && ((cpk >> (8 * y)) & 0xffu) >= dthr && dc >= dthr);
-                }
-    }
-    return r;
-}
-
-// The two BWA_plus walks of phase A, one 4-position step per template instance so that the recursion ends as soon as no
-// lane needs another step.  K = area * 256 + <position byte> is carried along (no per-position constants in registers);
-// the bounds are kept relative to the current step (r* = bound - 4 * g) and re-based once per step.  A step is
-// branch-free: "this lane visits position j" is the sign bit of a difference and gates the updates arithmetically, so
-// the four positions form one basic block with no exec-mask round trips through the scalar unit.
-template <int G, int ND, bool WINDOWED> struct Walk3 {
-    // rlow: the walk's last position (at_least_scan == 0 after it); rend: end of the window; rthr: window start + n2
-    template <bool ENDS>
-    static __device__ __forceinline__ void step(const uint32_t w, const int qoff_v, const int q_v, int &K, int &best, int &rlow, const int rend, const int rthr)
-    {
-#pragma unroll
-        for (int j = 3; j >= 0; --j) {
-            K -= 1;
-            int live = rlow - (j + 1);                       // < 0: j >= rlow
-            if (ENDS) live &= j - rend;                      // < 0: j < rend
-            int rs = live & ~K;                              // < 0: visited and area >= 0 before this position
-            if (WINDOWED || G == 0) rs &= rthr - j;          // < 0: j > rthr (always true above position 2 of an unwindowed read)
-            rlow = rs < 0 ? j - 2 : rlow;
-            const int t = qoff_v - (int)(int8_t)((w >> (8 * j)) & 0xffu);
-            const int dq = t < q_v ? t : q_v;                // Q - quality_score() = min(Q, Q + offset - (signed char)raw)
-            K += (dq & (live >> 31)) * 256;
-            best = best > K ? best : K;                      // (a lane that is not visiting only counts K down: never a new maximum)
-        }
-    }
-    static __device__ __forceinline__ void run(const uint32_t (&qd)[ND], const int qoff_v, const int q_v, int &K, int &best, int rlow, int rend, int rthr)
-    {
-        if (!__any(rlow <= 3)) return; // every lane is done (a lane whose window still ends below keeps rlow <= 3)
-        if (__any(rend < 4)) step<true>(qd[G], qoff_v, q_v, K, best, rlow, rend, rthr); // some window ends inside or below this step
-        else step<false>(qd[G], qoff_v, q_v, K, best, rlow, rend, rthr);
-        Walk3<G - 1, ND, WINDOWED>::run(qd, qoff_v, q_v, K, best, rlow + 4, rend + 4, rthr + 4);
-    }
-};
-template <int ND, bool WINDOWED> struct Walk3<-1, ND, WINDOWED> {
-    static __device__ __forceinline__ void run(const uint32_t (&)[ND], int, int, int &, int &, int, int, int) {}
-};
-template <int G, int ND, bool WINDOWED> struct Walk5 {
-    // rhigh: the walk's last position; rthr: final_pos_3 - n2 (resets need a position below it); rwa: window start
-    static __device__ __forceinline__ void run(const uint32_t (&qd)[ND], const int qoff_v, const int q_v, int &K, int &best, int rhigh, int rthr, int rwa)
-    {
-        if (!__any(rhigh >= 0)) return;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            K -= 1;
-            int live = (j - 1) - rhigh;                      // < 0: j <= rhigh
-            if (WINDOWED) live &= rwa - (j + 1);             // < 0: j >= rwa
-            const int rs = live & ~K & (j - rthr);           // < 0: visited, area >= 0 before, j < rthr
-            rhigh = rs < 0 ? j + 2 : rhigh;
-            const int t = qoff_v - (int)(int8_t)((qd[G] >> (8 * j)) & 0xffu);
-            const int dq = t < q_v ? t : q_v;
-            K += (dq & (live >> 31)) * 256;
-            best = best > K ? best : K;
-        }
-        Walk5<G + 1, ND, WINDOWED>::run(qd, qoff_v, q_v, K, best, rhigh - 4, rthr - 4, rwa - 4);
-    }
-};
-template <int ND, bool WINDOWED> struct Walk5<ND, ND, WINDOWED> {
-    static __device__ __forceinline__ void run(const uint32_t (&)[ND], int, int, int &, int &, int, int, int) {}
-};
-
-template <int C, int NW, bool WINDOWED, int LPR = 8, bool EXT = false>
-__global__ __launch_bounds__(NW * 64, tpr_bounds_waves(C, LPR, EXT)) void trim_tpr(
-    const DevParams P, const uint8_t *__restrict__ seq, const uint8_t *__restrict__ qual,
-    const uint32_t *__restrict__ off, const uint32_t n_reads, const uint32_t *__restrict__ ad_sl,
-    const uint16_t *__restrict__ ad_hit, uint2 *__restrict__ out, unsigned long long *__restrict__ rec_pre,
-    unsigned long long *__restrict__ rec_post, uint64_t *__restrict__ counters, uint32_t *__restrict__ err)
-{
-    static_assert(LPR == 8 || LPR == 4, "phase B runs 8 or 4 lanes per read");
-    using Cfg = RowCfg<C, LPR>;
-    using T = TprCfg<C, LPR>;
-    constexpr int D = Cfg::D, W = Cfg::W, NP = T::NP, ND = T::ND, NF = T::NF, NR = T::NR, NRX = NR ? NR : 1, NWORD = T::NWORD, NPOS = ND * 4;
-    static_assert(!Cfg::HQ8 && NPOS <= 255, "positions must fit the low byte of the argmax keys");
-    static_assert(ND >= 16, "the snapshot column doubles as the 16 transition counters of exact_base_pass");
-    static_assert(T::SROW * 4 == TPR_SROW_BYTES, "row stride");
-    static_assert(T::lds_dwords(NW) * 4 <= 160 * 1024, "LDS");
-    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-    uint32_t *hb = smem + Cfg::O_HB;
-    const uint32_t *t_lc = smem + Cfg::O_TLC;
-    const uint32_t *t_bm = smem + Cfg::O_TBM;
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int rl = lane & (LPR - 1);
-    const int rowb = lane & (64 - LPR);
-    const int wave = uni(tid >> 6);
-    const int pbase = rl * C;
-
-    for (int i = tid; i < Cfg::N_ZERO; i += NW * 64) smem[i] = 0u;
-    for (int i = tid; i < 256; i += NW * 64) {
-        const uint32_t w = P.base_tab[i];
-        smem[Cfg::O_TBASE + i] = w;
-        smem[T::O_T2 + 2 * i] = ((w >> BT_SHIFT(0)) & 1u) | (((w >> BT_SHIFT(1)) & 1u) << 8) | (((w >> BT_SHIFT(2)) & 1u) << 16) | (((w >> BT_SHIFT(3)) & 1u) << 24);
-        smem[T::O_T2 + 2 * i + 1] = (w >> 31) | (((w >> BT_SHIFT(4)) & 1u) << 1);
-    }
-    for (int i = tid; i <= W; i += NW * 64) {
-        smem[Cfg::O_TLC + i] = P.lc_thr[i];
-        smem[Cfg::O_TAVGQ + i] = (uint32_t)P.avgq_min_v[i];
-        smem[Cfg::O_TMAGIC + i] = P.div_magic[i];
-    }
-    for (int i = tid; i < Cfg::BMW * (C + 1); i += NW * 64) {
-        const int nb = med3i((i / Cfg::BMW) - 4 * (i % Cfg::BMW), 0, 4);
-        smem[Cfg::O_TBM + i] = nb >= 4 ? 0xffffffffu : ((1u << (8 * nb)) - 1u);
-    }
-    uint32_t two = 2u, three = 3u;
-    asm volatile("" : "+v"(two), "+v"(three)); // VGPR operands for the SDWA shifts
-    if (tid == 0 && blockIdx.x == 0 && (uint32_t)(size_t)((lds_u32_ptr)smem) != 0u) atomicOr(err, 4u);
-    __syncthreads();
-
-    const uint32_t total_chunks = (n_reads + 63) >> 6;
-    const uint32_t chunks_per_iter = gridDim.x * NW;
-    const uint32_t n_iter = (total_chunks + chunks_per_iter - 1) / chunks_per_iter;
-    constexpr uint32_t FLUSH_EVERY = 65535u / (NW * 64) > 0 ? 65535u / (NW * 64) : 1;
-    constexpr uint32_t REG_FLUSH_EVERY = LPR == 8 ? 7 : 15; // 6-bit fields: 7 chunks x 8 (15 x 4) reads per row <= 63
-
-    const int in_off = P.in_off, Q = P.Q;
-    const uint32_t snap_base = (uint32_t)(T::O_SNAP + wave * T::SNAP_WAVE + lane) * 4u; // LDS byte address of this lane's column
-    const uint32_t offb = ((uint32_t)in_off & 0xffu) * 0x01010101u;
-    const bool swar_ok = in_off >= 0 && in_off <= 86; // else every read takes the exact quality pass
-    uint32_t bpre[C], bpost[C];
-#pragma unroll
-    for (int j = 0; j < C; ++j) { bpre[j] = 0; bpost[j] = 0; }
-    uint32_t any_err = 0;
-    auto spill_base_regs = [&]() {
-#pragma unroll
-        for (int j = 0; j < C; ++j) {
-            const uint32_t x = bpre[j], y = bpost[j];
-            if (x) {
-#pragma unroll
-                for (int c = 0; c < FAQCS_NBASE; ++c) {
-                    const uint32_t v = ((x >> BT_SHIFT(c)) & 63u) | (((y >> BT_SHIFT(c)) & 63u) << 16);
-                    if (v) atomicAdd(&hb[c * W + pbase + j], v);
-                }
-            }
-            bpre[j] = 0; bpost[j] = 0;
-        }
-    };
-
-#pragma unroll 1
-    for (uint32_t it = 0; it < n_iter; ++it) {
-        const uint32_t chunk = (it * gridDim.x + blockIdx.x) * NW + wave;
-        if (chunk < total_chunks) {
-            const uint32_t base = chunk << 6;
-            const uint32_t my = base + lane;
-            const bool mine = my < n_reads;
-            const uint32_t v_off = mine ? off[my] : 0u;
-            const uint32_t v_len = mine ? off[my + 1] - v_off : 0u;
-            const uint32_t v_sl = (WINDOWED && ad_sl && mine) ? ad_sl[my] : (v_len << 16);
-            const uint32_t v_hit = (ad_hit && mine) ? ad_hit[my] : 0u;
-
-            // ---- software prefetch of the row's read 0 for phase B ----------------------------------------
-            PackedBytes<D> nseq; // (bases only: the qualities reach phase B through LDS)
-            int n_len = __shfl((int)v_len, rowb);
-            {
-                const uint32_t o = (uint32_t)__shfl((int)v_off, rowb);
-#pragma unroll
-                for (int k = 0; k < D; ++k) nseq.w[k] = 0;
-                if (pbase < n_len) nseq = *(const PackedBytes<D> *)(seq + (size_t)o + pbase);
-            }
-
-            // ================= phase A: one read per lane =====================================================
-            ReadOutcome oc;
-            uint32_t v_info, v_patch = 0; // what phase B needs: start | kept << 8 | valid << 16 | error << 17 | patch << 18 ; lead | trail << 8
-            {
-                const int len = (int)v_len;
-                uint32_t sd[ND], qd[ND];
-#pragma unroll
-                for (int k = 0; k < NF; ++k) {
-                    PackedBytes<4> ts, tq;
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) { ts.w[i] = 0u; tq.w[i] = offb; }
-                    if (16 * k < len) {
-                        ts = *(const PackedBytes<4> *)(seq + (size_t)v_off + 16 * k);
-                        tq = *(const PackedBytes<4> *)(qual + (size_t)v_off + 16 * k);
-                    }
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) { sd[4 * k + i] = ts.w[i]; qd[4 * k + i] = tq.w[i]; }
-                }
-                if (NR) {
-                    PackedBytes<NRX> ts, tq;
-#pragma unroll
-                    for (int i = 0; i < NR; ++i) { ts.w[i] = 0u; tq.w[i] = offb; }
-                    if (16 * NF < len) {
-                        ts = *(const PackedBytes<NRX> *)(seq + (size_t)v_off + 16 * NF);
-                        tq = *(const PackedBytes<NRX> *)(qual + (size_t)v_off + 16 * NF);
-                    }
-#pragma unroll
-                    for (int i = 0; i < NR; ++i) { sd[4 * NF + i] = ts.w[i]; qd[4 * NF + i] = tq.w[i]; }
-                }
-                uint32_t blast = 0; // last base (a lane without a read must not touch the arena: its offset is not one)
-                if (len) blast = (uint32_t)seq[(size_t)v_off + len - 1];
-                // bytes past the read inside its last 16-byte piece: base 0 (class "none"), quality == offset (q = 0, adds 0 to the sums)
-#pragma unroll
-                for (int k = 0; k < ND; ++k) {
-                    if (__any(len < 4 * k + 4 && 16 * (k >> 2) < len)) {
-                        const uint32_t m = low_bytes(med3i(len - 4 * k, 0, 4));
-                        sd[k] &= m;
-                        qd[k] = (qd[k] & m) | (offb & ~m);
-                    }
-                }
-
-                // ---- classes: A,T,C,G counts (8-bit fields) with a prefix snapshot per dword, upper-case N bits ----
-                uint32_t cnt4 = 0, nub[NWORD];
-#pragma unroll
-                for (int w = 0; w < NWORD; ++w) nub[w] = 0;
-#pragma unroll
-                for (int k = 0; k < ND; ++k) {
-                    lds_store_u32(snap_base + (uint32_t)k * (uint32_t)(TPR_SROW_BYTES), cnt4);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const uint32_t ad = (j == 0 ? byte_times8<0>(sd[k], three) : j == 1 ? byte_times8<1>(sd[k], three)
-                                             : j == 2 ? byte_times8<2>(sd[k], three) : byte_times8<3>(sd[k], three)) + (uint32_t)(T::O_T2 * 4);
-                        const LdsPair e = *(lds_u2_ptr)(size_t)ad;
-                        cnt4 += e.x;
-                        nub[(4 * k + j) >> 5] = __builtin_amdgcn_alignbit(e.y, nub[(4 * k + j) >> 5], 1); // bit (p & 31) = upper-case N at p
-                    }
-                }
-                if ((NPOS & 31) != 0) nub[NWORD - 1] >>= (32 - (NPOS & 31));
-                const int nACGT = (int)__builtin_amdgcn_sad_u8(cnt4, 0u, 0u);
-                int nup = 0;
-#pragma unroll
-                for (int w = 0; w < NWORD; ++w) nup += __builtin_popcount(nub[w]);
-                const bool abn_seq = nACGT + nup != len; // a letter that is neither ACGT (any case) nor 'N'
-
-                // ---- mask_quality_terminal_N (trim.cpp:1191-1216): upper-case 'N' runs at either end get Q0 -----
-                const bool tn = len > 0 && ((nub[0] & 1u) != 0u || blast == 'N');
-                if (__any(tn)) {
-                    int lead = NPOS, trail = 0;
-#pragma unroll
-                    for (int w = NWORD - 1; w >= 0; --w) { // first position that is not N
-                        const uint32_t x = ~nub[w];
-                        lead = x ? 32 * w + __builtin_ctz(x) : lead;
-                    }
-                    lead = lead < len ? lead : len;
-#pragma unroll
-                    for (int w = 0; w < NWORD; ++w) { // 1 + last position that is not N
-                        const uint32_t x = ~nub[w] & bit_range(0, med3i(len - 32 * w, 0, 32));
-                        trail = x ? 32 * w + 32 - __builtin_clz(x) : trail;
-                    }
-                    if (!tn) { lead = 0; trail = len; }
-                    v_patch = (uint32_t)lead | ((uint32_t)trail << 8);
-#pragma unroll
-                    for (int k = 0; k < ND; ++k) {
-                        if (!__any(lead > 4 * k || (trail < 4 * k + 4 && 4 * k < len))) continue;
-                        const uint32_t m1 = low_bytes(med3i(lead - 4 * k, 0, 4));   // positions < lead
-                        const uint32_t m2 = ~low_bytes(med3i(trail - 4 * k, 0, 4)); // positions >= trail (past the read: already == offset)
-                        const uint32_t m = m1 | m2;
-                        qd[k] = (qd[k] & ~m) | (offb & m);
-                    }
-                }
-
-                // ---- quality: sum and range check, four bytes per instruction --------------------------------
-                // V = sum(raw - offset); a byte outside [offset, offset + 41] (or >= 128) sends the read to the exact pass
-                uint32_t qsum = 0, qbad = 0, qor = 0;
-#pragma unroll
-                for (int k = 0; k < ND; ++k) {
-                    qsum = __builtin_amdgcn_sad_u8(qd[k], 0u, qsum);
-                    const uint32_t t = (qd[k] | 0x80808080u) - offb;                      // byte: 128 + raw - offset (raw < 128)
-                    const uint32_t s = (t & 0x7f7f7f7fu) + 0x56565656u;                   // bit 7: raw - offset > 41
-                    qbad |= ~t | s;                                                       // bit 7 clear in t: raw < offset
-                    qor |= qd[k];
-                }
-                const bool badq = !swar_ok || (((qbad | qor) & 0x80808080u) != 0u);
-                int V_pre = (int)qsum - NPOS * in_off;
-                bool read_err = false;
-
-                // ---- the window the reference trims: after the adapter pre-pass and --5end/--3end (trim.cpp:270-314) ----
-                int wa = 0, wn = len;
-                uint32_t flags = 0, filt = 0;
-                if (WINDOWED && P.has_adapters) {
-                    const int first = (int)(v_sl & 0xffffu), second = (int)(v_sl >> 16);
-                    const bool mod = len != second;
-                    wa = mod ? first : 0; wn = mod ? second : len;
-                    flags = mod ? FAQCS_F_ADAPTER : 0u;
-                }
-                if (WINDOWED && P.trim5) {
-                    const bool over = (int)P.trim5 > wn;
-                    wa = over ? wa : wa + (int)P.trim5;
-                    wn = over ? 0 : wn - (int)P.trim5;
-                }
-                if (WINDOWED && P.trim3) wn = (int)P.trim3 > wn ? 0 : wn - (int)P.trim3;
-
-                // ---- BWA_plus (trim.cpp:714-793), walked as the reference walks it -----------------------------
-                const int a5 = wn < 5 ? wn : 5, nn2 = wn < 2 ? wn : 2, wend = wa + wn;
-                int qoff_v = Q + in_off, q_v = Q;
-                asm volatile("" : "+v"(qoff_v), "+v"(q_v));
-                // Q - quality_score(p) = min(Q, Q + offset - (signed char)raw)
-                // 3' walk.  at_least_scan == 0 after position p  <=>  p == lowp: the walk covers min(5, n) positions, and a
-                // reset at p (p > n2 and area >= 0 before p) moves its end to p - 2 (n2 == 2 whenever a reset can fire).
-                // best = maxArea << 8 | position of the first maximum.
-                int best = 255, K3 = NPOS;
-                Walk3<ND - 1, ND, WINDOWED>::run(qd, qoff_v, q_v, K3, best, (wn > 0 ? wend - a5 : NPOS) - 4 * (ND - 1), wend - 4 * (ND - 1),
-                                                 wa + nn2 - 4 * (ND - 1));
-                const int S3 = best >> 8;
-                const int fp3 = S3 > 0 ? (best & 255) - 1 - wa : wn - 1;
-                // 5' walk (trim.cpp:752-779): resets need pos_5 < final_pos_3 - n2; the FIRST maximum wins (low byte = 255 - p)
-                int best5 = 255, K5 = 256;
-                if (!(EXT && P.protect5)) // --5trim_off (trim.cpp:752)
-                    Walk5<0, ND, WINDOWED>::run(qd, qoff_v, q_v, K5, best5, wn > 0 ? wa + a5 - 1 : -1, wa + fp3 - nn2, wa);
-                const int S5 = best5 >> 8;
-                const int fp5 = S5 > 0 ? (255 - (best5 & 255)) + 1 - wa : 0;
-
-                // ---- length filters and the kept window (trim.cpp:317-360) -------------------------------------
-                int a = wa, n = wn;
-                bool ret = mine;
-                uint32_t qt_removed = 0;
-                if (ret && (n < (int)P.min_len || n == 0)) { ret = false; filt = FAQCS_FILT_LENGTH_PRE; }
-                if (ret) {
-                    const int kept = fp3 <= fp5 ? 0 : fp3 - fp5 + 1;
-                    if (kept != n) { qt_removed = (uint32_t)(n - kept); flags |= FAQCS_F_QUAL_TRIMMED; }
-                    a += fp5;
-                    n = kept;
-                    if (n < (int)P.min_len || n == 0) { ret = false; filt = FAQCS_FILT_LENGTH_POST; }
-                }
-
-                // ---- poly-N (trim.cpp:363-371, :578-597): -n 2 = two adjacent upper-case N inside the kept window ----
-                if (EXT && P.max_poly_n != 2u) { // -n 0: every read trips; -n 1: any upper-case N inside the kept window
-                    uint32_t hit = 0;
-#pragma unroll
-                    for (int w = 0; w < NWORD; ++w) hit |= nub[w] & bit_range(med3i(a - 32 * w, 0, 32), med3i(a + n - 32 * w, 0, 32));
-                    if (ret && (P.max_poly_n == 0u || hit != 0u)) { flags |= FAQCS_F_POLY_N_SEEN; ret = false; filt = FAQCS_FILT_POLY_N; }
-                } else {
-                    uint32_t pr[NWORD], anyp = 0; // bit e: N at e - 1 and at e
-#pragma unroll
-                    for (int w = 0; w < NWORD; ++w) {
-                        pr[w] = nub[w] & ((nub[w] << 1) | (w ? nub[w - 1] >> 31 : 0u));
-                        anyp |= pr[w];
-                    }
-                    if (__any(ret && anyp != 0u)) {
-                        uint32_t hit = 0;
-#pragma unroll
-                        for (int w = 0; w < NWORD; ++w) hit |= pr[w] & bit_range(med3i(a + 1 - 32 * w, 0, 32), med3i(a + n - 32 * w, 0, 32));
-                        if (ret && hit != 0u) { flags |= FAQCS_F_POLY_N_SEEN; ret = false; filt = FAQCS_FILT_POLY_N; }
-                    }
-                }
-
-                // ---- base counts before / inside the kept window (trim.cpp:390-403, :810-875) ---------------------
-                // prefix(x) = snapshot of dword x >> 2 plus the x & 3 bytes in front of x (one 4-byte load from the arena)
-                auto prefix4 = [&](int x) -> uint32_t {
-                    uint32_t c = lds_load_u32(snap_base + (uint32_t)(x < NPOS ? x >> 2 : 0) * (uint32_t)(TPR_SROW_BYTES));
-                    c = x < NPOS ? c : cnt4; // (the whole read)
-                    if (__any((x & 3) != 0)) {
-                        uint32_t w = 0;
-                        if (x & 3) w = ((const PackedBytes<1> *)(seq + (size_t)v_off + (x & ~3)))->w[0] & low_bytes(x & 3);
-                        c += ((lds_u2_ptr)(size_t)(byte_times8<0>(w, three) + (uint32_t)(T::O_T2 * 4)))->x;
-                        c += ((lds_u2_ptr)(size_t)(byte_times8<1>(w, three) + (uint32_t)(T::O_T2 * 4)))->x;
-                        c += ((lds_u2_ptr)(size_t)(byte_times8<2>(w, three) + (uint32_t)(T::O_T2 * 4)))->x;
-                    }
-                    return c;
-                };
-                uint32_t c4post = cnt4;
-                if (__any(ret && (a != 0 || n != len))) {
-                    c4post = prefix4(a + n);
-                    if (__any(a != 0)) c4post -= prefix4(a);
-                }
-                const uint32_t pA = cnt4 & 0xffu, pT = (cnt4 >> 8) & 0xffu, pC = (cnt4 >> 16) & 0xffu, pG = cnt4 >> 24;
-                const uint32_t cA = c4post & 0xffu, cT = (c4post >> 8) & 0xffu, cC = (c4post >> 16) & 0xffu, cG = c4post >> 24;
-                uint32_t pN = (uint32_t)(len - nACGT), cN = (uint32_t)n - (cA + cT + cC + cG); // (exact pass below when abn_seq)
-
-                // ---- sum(raw - offset) over the kept window (trim.cpp:374, :553-576) ---------------------------
-                int V_post;
-                if (!WINDOWED) {
-                    // all v == q here (no byte below the offset): sum q over the kept window from the two walks' areas
-                    const int Tsum = len * Q - V_pre; // sum of (Q - q) over the read
-                    V_post = n * Q - (Tsum - (S3 > 0 ? S3 : 0) - (S5 > 0 ? S5 : 0));
-                } else {
-                    uint32_t s = 0;
-#pragma unroll
-                    for (int k = 0; k < ND; ++k) {
-                        const uint32_t m = low_bytes(med3i(a + n - 4 * k, 0, 4)) & ~low_bytes(med3i(a - 4 * k, 0, 4));
-                        s = __builtin_amdgcn_sad_u8(qd[k] & m, 0u, s);
-                    }
-                    V_post = (int)s - n * in_off;
-                }
-                // exact pass for a read with a raw quality outside [offset, offset + 41] (fastq.h:17-36: negative scores clamp
-                // to 0 in the trimmers but not in the averages; > 41 aborts the run)
-                if (__any(badq)) {
-                    const ExactQuality xq = exact_quality_pass<NP>(qual, v_off, len, tn ? v_patch : ((uint32_t)len << 8), a, n, in_off);
-                    if (badq) { V_pre = xq.sv; V_post = xq.svp; read_err = xq.mq > 41; }
-                }
-
-                // ---- average quality (trim.cpp:374-382) -------------------------------------------------------------
-                if (EXT && P.avgq_on && ret && V_post < ((const int32_t *)(smem + Cfg::O_TAVGQ))[n]) { ret = false; filt = FAQCS_FILT_AVG_Q; }
-
-                // ---- low-complexity filter (trim.cpp:405-513) ---------------------------------------------------
-                bool lc_trip = false, dinuc = false;
-                uint32_t dthr = 0;
-                if (ret) {
-                    const uint32_t thr = t_lc[n];
-                    const uint32_t mthr = thr & 0xffffu;
-                    dthr = thr >> 16;
-                    lc_trip = cA >= mthr || cT >= mthr || cG >= mthr || cC >= mthr;
-                    // dc[X->Y] <= min(count X, count Y): only pairs whose two counts both reach dthr can trip
-                    dinuc = !lc_trip && ((cA >= dthr) + (cT >= dthr) + (cC >= dthr) + (cG >= dthr)) >= 2;
-                }
-                // exact per-position pass over the bases: N counts for reads with other letters, transition counts for
-                // dinucleotide candidates (both rare; the lane's snapshot column is free by now and holds the 16 counters)
-                if (__any(abn_seq || dinuc)) {
-                    const uint32_t cpk = cA | (cT << 8) | (cC << 16) | (cG << 24);
-                    const ExactBases xb = exact_base_pass<NP>(seq, v_off, len, a, n, dinuc, dthr, cpk, snap_base, (uint32_t)(T::O_T2 * 4));
-                    if (abn_seq) { pN = xb.npre; cN = xb.npost; }
-                    if (dinuc) lc_trip = lc_trip || xb.trip;
-                }
-                if (ret && lc_trip) { ret = false; filt = FAQCS_FILT_LOW_COMPLEXITY; }
-
-                if (read_err) { any_err = 1; flags |= FAQCS_F_ERR_QUALITY; }
-                oc.an = (uint32_t)a | ((uint32_t)n << 16);
-                oc.fl = flags | (ret ? FAQCS_F_VALID : 0u) | (filt << FAQCS_F_FILTER_SHIFT) | (qt_removed << 20);
-                oc.pAT = pA | (pT << 16); oc.pCG = pC | (pG << 16);
-                oc.cAT = cA | (cT << 16); oc.cCG = cC | (cG << 16);
-                oc.N = pN | (cN << 16);
-                oc.Vpre = V_pre; oc.Vpost = V_post;
-                v_info = (uint32_t)a | ((uint32_t)n << 8) | (ret ? 1u << 16 : 0u) | (read_err ? 1u << 17 : 0u);
-                // the snapshots are spent: the column now carries this read's quality bytes (terminal-N runs already at the
-                // offset, bytes past the read too) to the 8 lanes that accumulate it in phase B
-#pragma unroll
-                for (int k = 0; k < ND; ++k) lds_store_u32(snap_base + (uint32_t)k * (uint32_t)(TPR_SROW_BYTES), qd[k]);
-            }
-
-            // ================= phase B: 8 lanes per read, accumulate only ====================================
-            const uint32_t qcol = (uint32_t)(T::O_SNAP + wave * T::SNAP_WAVE) * 4u; // LDS byte address of the wave's column block
-#pragma unroll 1
-            for (int t = 0; t < LPR; ++t) {
-                if (base + (uint32_t)t >= n_reads) break; // wave-uniform: no row has a read left
-                const int len = n_len;
-                const bool act = base + (uint32_t)(rowb + t) < n_reads;
-                uint32_t ws[D], wq[D];
-#pragma unroll
-                for (int k = 0; k < D; ++k) ws[k] = nseq.w[k];
-                const uint32_t info = (uint32_t)__shfl((int)v_info, rowb + t);
-                if (t + 1 < LPR) {
-                    n_len = __shfl((int)v_len, rowb + t + 1);
-                    const uint32_t o = (uint32_t)__shfl((int)v_off, rowb + t + 1);
-#pragma unroll
-                    for (int k = 0; k < D; ++k) nseq.w[k] = 0;
-                    if (pbase < n_len) nseq = *(const PackedBytes<D> *)(seq + (size_t)o + pbase);
-                }
-                { // zero the base bytes past the end of the read (the last dword of a lane may over-read 1..3 bytes)
-                    const int vb = med3i(len - pbase, 0, C);
-                    const uint4 bm = *reinterpret_cast<const uint4 *>(t_bm + Cfg::BMW * vb);
-                    uint32_t m[8] = {bm.x, bm.y, bm.z, bm.w, 0u, 0u, 0u, 0u};
-                    if (D > 4) {
-                        const uint4 bm2 = *reinterpret_cast<const uint4 *>(t_bm + Cfg::BMW * vb + 4);
-                        m[4] = bm2.x; m[5] = bm2.y; m[6] = bm2.z; m[7] = bm2.w;
-                    }
-#pragma unroll
-                    for (int k = 0; k < D; ++k) ws[k] &= m[k];
-                }
-                { // the lane's C quality bytes out of the owner's column: dwords pbase / 4 ..., shifted into place
-                    const uint32_t col = qcol + (uint32_t)(rowb + t) * 4u;
-                    uint32_t rq[D + 1];
-#pragma unroll
-                    for (int i = 0; i <= D; ++i) {
-                        const int row = (pbase >> 2) + i;
-                        rq[i] = lds_load_u32(col + (uint32_t)(row < ND ? row : ND - 1) * (uint32_t)(TPR_SROW_BYTES));
-                    }
-#pragma unroll
-                    for (int i = 0; i < D; ++i) wq[i] = __builtin_amdgcn_alignbyte(rq[i + 1], rq[i], (uint32_t)(pbase & 3));
-                }
-                const int a = (int)(info & 0xffu), n = (int)((info >> 8) & 0xffu);
-                const bool ret = ((info >> 16) & 1u) != 0u, read_err = ((info >> 17) & 1u) != 0u;
-                uint32_t incf[C];
-                BaseLookup<C, 0>::run((uint32_t)(Cfg::O_TBASE * 4), ws, two, incf);
-                int q[C];
-#pragma unroll
-                for (int j = 0; j < C; ++j) {
-                    const int v = (int)(int8_t)((wq[j >> 2] >> (8 * (j & 3))) & 0xffu) - in_off;
-                    q[j] = v < 0 ? 0 : v;
-                }
-                if (__any(read_err)) { // rare: keep the row's table indices in range, count nothing (fastq.h:31-33 aborts the run)
-#pragma unroll
-                    for (int j = 0; j < C; ++j) { q[j] = read_err ? 0 : q[j]; incf[j] = read_err ? 0u : incf[j]; }
-                }
-                // a position outside the read adds to quality column 0 (flush_block subtracts those) and class "none"
-                const uint32_t counted = (act && !read_err) ? 1u : 0u;
-                const uint32_t pb4 = 4u * (uint32_t)pbase;
-                const uint32_t postm = ret ? range_mask<C>(a, a + n, pbase) : 0u;
-#pragma unroll
-                for (int j = 0; j < C; ++j) {
-                    lds_add_u32(__umul24((uint32_t)q[j], (uint32_t)(W * 4)) + pb4 + (uint32_t)(Cfg::O_HQ * 4 + 4 * j),
-                                counted | ((uint32_t)bit_m1(postm, j) & 0x10000u));
-                    bpre[j] += incf[j];
-                    bpost[j] += incf[j] & (uint32_t)bit_m1(postm, j);
-                }
-            }
-
-            // ---- chunk epilogue: one read per lane ----------------------------------------------------------
-            chunk_epilogue<LPR>(oc, mine, my, v_len, v_hit, lane, smem + Cfg::O_LEN, smem + Cfg::O_RQ, smem + Cfg::O_BQPRE,
-                                smem + Cfg::O_BQPOST, smem + Cfg::O_FS, smem + Cfg::O_TMAGIC, out, rec_pre, rec_post, EXT && P.avgq_on != 0, 0u);
-        }
-
-        const bool block_flush = ((it + 1) % FLUSH_EVERY) == 0 || it + 1 == n_iter;
-        if (((it + 1) % REG_FLUSH_EVERY) == 0 || block_flush) spill_base_regs();
-        if (block_flush) flush_block<C, LPR, NW>(smem, counters, P.R, tid);
-    }
-    if (__any(any_err != 0) && lane == 0) atomicOr(err, 1u);
-}
-
-// ---------------------------------------------------------------------------------------------------------
 // composition_histogram: update_base_statistics()'s composition part (trim.cpp:860-874) from the per-read
 // records.  One thread per record; the block's LDS holds the whole 10 001 x 6 table as 16-bit counters
 // (two per dword), flushed to the global u64 block before any of them can overflow.
@@ -1363,28 +727,12 @@ static hipError_t launch_trim_t(const DevParams &P, const uint8_t *seq, const ui
     return hipGetLastError();
 }
 
-template <int C, int NW, bool WINDOWED, int LPR = 8, bool EXT = false>
-static hipError_t launch_trim_tpr(const DevParams &P, const uint8_t *seq, const uint8_t *qual, const uint32_t *off,
-                                  uint32_t n_reads, const uint32_t *ad_sl, const uint16_t *ad_hit, faqcs_read_result *out,
-                                  unsigned long long *rec_pre, unsigned long long *rec_post, uint64_t *counters, uint32_t *err,
-                                  int n_cu, hipStream_t st)
+// the four (WINDOWED, GENERIC) variants of one <C, LPR, NW> shape
+template <int C, int LPR, int NW, class... Args>
+static hipError_t launch_trim_variant(const bool windowed, const bool generic, const Args &...args)
 {
-    constexpr size_t lds = (size_t)TprCfg<C, LPR>::lds_dwords(NW) * 4;
-    static unsigned long long attr_done = 0;
-    auto kern = trim_tpr<C, NW, WINDOWED, LPR, EXT>;
-    if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds, attr_done); e != hipSuccess) return e;
-    const uint32_t chunks = (n_reads + 63) / 64;
-    int blocks_per_cu = (int)((160 * 1024) / lds);
-    const int by_waves = (4 * tpr_waves_per_simd(C, LPR, EXT) + NW - 1) / NW;
-    if (blocks_per_cu > by_waves) blocks_per_cu = by_waves;
-    if (blocks_per_cu < 1) blocks_per_cu = 1;
-    uint32_t grid = (chunks + NW - 1) / NW;
-    const uint32_t cap = (uint32_t)(n_cu * blocks_per_cu);
-    if (grid > cap) grid = cap;
-    if (grid == 0) return hipSuccess;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, st, P, seq, qual, off, n_reads, ad_sl, ad_hit,
-                       reinterpret_cast<uint2 *>(out), rec_pre, rec_post, counters, err);
-    return hipGetLastError();
+    return windowed ? (generic ? launch_trim_t<C, LPR, NW, true, true>(args...) : launch_trim_t<C, LPR, NW, true, false>(args...))
+                    : (generic ? launch_trim_t<C, LPR, NW, false, true>(args...) : launch_trim_t<C, LPR, NW, false, false>(args...));
 }
 
 hipError_t faqcs_launch_trim_long(const DevParams &P, const uint8_t *seq, const uint8_t *qual, const uint32_t *off, uint32_t n_reads,
@@ -1428,77 +776,25 @@ hipError_t faqcs_launch_trim(const DevParams &P, const uint8_t *seq, const uint8
     const bool windowed = P.has_adapters || ((P.trim5 || P.trim3) && !P.qc_only);
     const bool generic = !(P.mode == FAQCS_MODE_BWA_PLUS && !P.protect5 && !P.qc_only && P.replace_q == 0 && !P.avgq_on &&
                            P.max_poly_n == 2 && P.dbg == 0);
+    // one table of "longest read of the batch" -> <C, LPR, NW>; beside each row the lengths that reach it and how.  The lengths trim_lds owns
+    // (1 ... 304) arrive here with --replace_to_N_q or a FAQCS_DBG bit (GENERIC only), with FAQCS_TRIM_LDS=0 (every option set; FAQCS_TRIM_LDS4=0:
+    // <= 76, FAQCS_TRIM_LDS16=0: 153 ... 304), and when a submission holds more chunks than trim_lds's blocks can take between two flushes.
+    constexpr int NW = FAQCS_TRIM_NW;
 #define FAQCS_TRIM_ARGS P, seq, qual, off, n_reads, ad_sl, ad_hit, out, rec_pre, rec_post, counters, err, n_cu, st
-#define FAQCS_TRIM_CASE(C, NW)                                                                              \
-    return windowed ? (generic ? launch_trim_t<C, 16, NW, true, true>(FAQCS_TRIM_ARGS) : launch_trim_t<C, 16, NW, true, false>(FAQCS_TRIM_ARGS)) \
-                    : (generic ? launch_trim_t<C, 16, NW, false, true>(FAQCS_TRIM_ARGS) : launch_trim_t<C, 16, NW, false, false>(FAQCS_TRIM_ARGS))
-    {   // 8 lanes per read: the headline shape (reads <= 160 bases, default option set); FAQCS_TRIM_LPR8=0 switches it off
-        static const bool lpr8 = [] { const char *e = getenv("FAQCS_TRIM_LPR8"); return !e || atoi(e) != 0; }();
-#define FAQCS_TRIM_CASE8(C)                                                                                 \
-    return windowed ? (generic ? launch_trim_t<C, 8, FAQCS_TRIM_NW, true, true>(FAQCS_TRIM_ARGS) : launch_trim_t<C, 8, FAQCS_TRIM_NW, true, false>(FAQCS_TRIM_ARGS)) \
-                    : (generic ? launch_trim_t<C, 8, FAQCS_TRIM_NW, false, true>(FAQCS_TRIM_ARGS) : launch_trim_t<C, 8, FAQCS_TRIM_NW, false, false>(FAQCS_TRIM_ARGS))
-        // trim_tpr (round 1's two-phase kernel) is NOT part of the shipped library since round 6: every batch it took runs trim_lds, its
-        // instantiations were 2.8 MB of a 4.8 MB library and most of every rebuild.  -DFAQCS_WITH_TRIM_TPR compiles them in again for A/B
-        // runs (FAQCS_TRIM_LDS=0 then reaches them as in rounds 4-5); without it FAQCS_TRIM_LDS=0 goes straight to trim_filter_accumulate.
-#ifdef FAQCS_WITH_TRIM_TPR
-        {   // the two-phase kernel for the headline option set; FAQCS_TRIM_TPR=0 switches it off
-            static const bool tpr = [] { const char *e = getenv("FAQCS_TRIM_TPR"); return !e || atoi(e) != 0; }();
-            // EXT: the default set plus --5trim_off / --avg_q / -n 0 or 1 (compiled apart so that the default variants stay as they are)
-            const bool ext = generic && P.mode == FAQCS_MODE_BWA_PLUS && !P.qc_only && P.replace_q == 0 && P.max_poly_n <= 2 && P.dbg == 0;
-#define FAQCS_TRIM_CASE_TPR(C) \
-    { g_last_trim_kernel = "trim_tpr"; \
-    return ext ? (windowed ? launch_trim_tpr<C, tpr_nw(C, 8, true), true, 8, true>(FAQCS_TRIM_ARGS) : launch_trim_tpr<C, tpr_nw(C, 8, true), false, 8, true>(FAQCS_TRIM_ARGS)) \
-               : (windowed ? launch_trim_tpr<C, tpr_nw(C), true>(FAQCS_TRIM_ARGS) : launch_trim_tpr<C, tpr_nw(C), false>(FAQCS_TRIM_ARGS)); }
-            if (lpr8 && tpr && (!generic || ext) && max_len > 76 && max_len <= 104) FAQCS_TRIM_CASE_TPR(13);   // 2x100
-            if (lpr8 && tpr && (!generic || ext) && max_len > 104 && max_len <= 152) FAQCS_TRIM_CASE_TPR(19);  // 2x150
-            if (lpr8 && tpr && !generic && max_len > 152 && max_len <= 160) FAQCS_TRIM_CASE_TPR(20);
-#undef FAQCS_TRIM_CASE_TPR
-#define FAQCS_TRIM_CASE_TPR4(C) \
-    { g_last_trim_kernel = "trim_tpr"; \
-    return ext ? (windowed ? launch_trim_tpr<C, tpr_nw(C, 4), true, 4, true>(FAQCS_TRIM_ARGS) : launch_trim_tpr<C, tpr_nw(C, 4), false, 4, true>(FAQCS_TRIM_ARGS)) \
-               : (windowed ? launch_trim_tpr<C, tpr_nw(C, 4), true, 4>(FAQCS_TRIM_ARGS) : launch_trim_tpr<C, tpr_nw(C, 4), false, 4>(FAQCS_TRIM_ARGS)); }
-            {   // reads <= 76 bases: 4 lanes per read in phase B (2x75, 2x50)
-                static const bool lpr4t = [] { const char *e = getenv("FAQCS_TRIM_LPR4"); return !e || atoi(e) != 0; }();
-                if (lpr4t && tpr && (!generic || ext) && max_len > 0 && max_len <= 64) FAQCS_TRIM_CASE_TPR4(16);
-                if (lpr4t && tpr && (!generic || ext) && max_len > 64 && max_len <= 76) FAQCS_TRIM_CASE_TPR4(19);
-            }
-#undef FAQCS_TRIM_CASE_TPR4
-        }
-#endif
-        {   // 4 lanes per read (16 reads per wave): reads <= 76 bases (2x75, 2x50); FAQCS_TRIM_LPR4=0 switches it off
-            static const bool lpr4 = [] { const char *e = getenv("FAQCS_TRIM_LPR4"); return !e || atoi(e) != 0; }();
-#define FAQCS_TRIM_CASE4(C)                                                                                 \
-    return windowed ? (generic ? launch_trim_t<C, 4, FAQCS_TRIM_NW, true, true>(FAQCS_TRIM_ARGS) : launch_trim_t<C, 4, FAQCS_TRIM_NW, true, false>(FAQCS_TRIM_ARGS)) \
-                    : (generic ? launch_trim_t<C, 4, FAQCS_TRIM_NW, false, true>(FAQCS_TRIM_ARGS) : launch_trim_t<C, 4, FAQCS_TRIM_NW, false, false>(FAQCS_TRIM_ARGS))
-            if (lpr4 && max_len <= 64) FAQCS_TRIM_CASE4(16);
-            if (lpr4 && max_len <= 76) FAQCS_TRIM_CASE4(19);
-#undef FAQCS_TRIM_CASE4
-        }
-        if (lpr8 && max_len <= 64) FAQCS_TRIM_CASE8(8);
-        if (lpr8 && max_len <= 104) FAQCS_TRIM_CASE8(13);   // 2x100
-        if (lpr8 && max_len <= 128) FAQCS_TRIM_CASE8(16);
-        if (lpr8 && max_len <= 152) FAQCS_TRIM_CASE8(19);   // 2x150: 152 position slots instead of 160
-        if (lpr8 && max_len <= 160) FAQCS_TRIM_CASE8(20);
-#undef FAQCS_TRIM_CASE8
-    }
-    // 16 lanes per read: 161..256 bases (and the A/B fallback of the 8-lane variants)
-    if (max_len <= 208) FAQCS_TRIM_CASE(13, FAQCS_TRIM_NW);
-    if (max_len <= 256) FAQCS_TRIM_CASE(16, FAQCS_TRIM_NW);
-    // long reads: the whole wave on one read, one superset variant per width (MiSeq 2x300 -> C = 5)
-    {   // two reads per wave (32 lanes each) up to 512 bases; FAQCS_TRIM_LPR32=0 falls back to the whole wave per read
-        static const bool lpr32 = [] { const char *e = getenv("FAQCS_TRIM_LPR32"); return !e || atoi(e) != 0; }();
-        if (lpr32 && max_len <= 320) // MiSeq 2x300: all four option variants like the short-read kernels
-            return windowed ? (generic ? launch_trim_t<10, 32, FAQCS_TRIM_NW, true, true>(FAQCS_TRIM_ARGS) : launch_trim_t<10, 32, FAQCS_TRIM_NW, true, false>(FAQCS_TRIM_ARGS))
-                            : (generic ? launch_trim_t<10, 32, FAQCS_TRIM_NW, false, true>(FAQCS_TRIM_ARGS) : launch_trim_t<10, 32, FAQCS_TRIM_NW, false, false>(FAQCS_TRIM_ARGS));
-        if (lpr32 && max_len <= 512)
-            return (windowed || generic) ? launch_trim_t<16, 32, FAQCS_TRIM_NW, true, true>(FAQCS_TRIM_ARGS)
-                                         : launch_trim_t<16, 32, FAQCS_TRIM_NW, false, false>(FAQCS_TRIM_ARGS);
-    }
-    if (max_len <= 320) return launch_trim_t<5, 64, FAQCS_TRIM_NW, true, true>(FAQCS_TRIM_ARGS);
-    if (max_len <= 512) return launch_trim_t<8, 64, FAQCS_TRIM_NW, true, true>(FAQCS_TRIM_ARGS);
-    if (max_len <= 768) return launch_trim_t<12, 64, FAQCS_TRIM_NW, true, true>(FAQCS_TRIM_ARGS);
-    if (max_len <= 1024) return launch_trim_t<16, 64, 8, true, true>(FAQCS_TRIM_ARGS); // 8 x 16 reads <= 255 per 8-bit cell
-#undef FAQCS_TRIM_CASE
+    if (max_len <= 64) return launch_trim_variant<16, 4, NW>(windowed, generic, FAQCS_TRIM_ARGS);   //   0 ... 64    4 lanes per read (2x50)
+    if (max_len <= 76) return launch_trim_variant<19, 4, NW>(windowed, generic, FAQCS_TRIM_ARGS);   //  65 ... 76    (2x75)
+    if (max_len <= 104) return launch_trim_variant<13, 8, NW>(windowed, generic, FAQCS_TRIM_ARGS);  //  77 ... 104   8 lanes per read (2x100)
+    if (max_len <= 128) return launch_trim_variant<16, 8, NW>(windowed, generic, FAQCS_TRIM_ARGS);  // 105 ... 128
+    if (max_len <= 152) return launch_trim_variant<19, 8, NW>(windowed, generic, FAQCS_TRIM_ARGS);  // 129 ... 152   (2x150: 152 position slots instead of 160)
+    if (max_len <= 160) return launch_trim_variant<20, 8, NW>(windowed, generic, FAQCS_TRIM_ARGS);  // 153 ... 160
+    if (max_len <= 208) return launch_trim_variant<13, 16, NW>(windowed, generic, FAQCS_TRIM_ARGS); // 161 ... 208   16 lanes per read
+    if (max_len <= 256) return launch_trim_variant<16, 16, NW>(windowed, generic, FAQCS_TRIM_ARGS); // 209 ... 256   (2x250)
+    if (max_len <= 320) return launch_trim_variant<10, 32, NW>(windowed, generic, FAQCS_TRIM_ARGS); // 257 ... 320   two reads per wave (MiSeq 2x300); 305 ... 320 with every option set
+    // longer reads, always here: one superset variant per width (the 512-base case keeps the default-set variant as well)
+    if (max_len <= 512) // 321 ... 512
+        return (windowed || generic) ? launch_trim_t<16, 32, NW, true, true>(FAQCS_TRIM_ARGS) : launch_trim_t<16, 32, NW, false, false>(FAQCS_TRIM_ARGS);
+    if (max_len <= 768) return launch_trim_t<12, 64, NW, true, true>(FAQCS_TRIM_ARGS);  // 513 ... 768   the whole wave on one read
+    if (max_len <= 1024) return launch_trim_t<16, 64, 8, true, true>(FAQCS_TRIM_ARGS);  // 769 ... 1 024 (8 waves x 16 reads <= 255 per 8-bit cell)
 #undef FAQCS_TRIM_ARGS
     return hipErrorInvalidValue;
 }

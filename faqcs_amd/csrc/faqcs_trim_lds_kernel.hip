@@ -1578,6 +1578,14 @@ static hipError_t launch_trim_lds(const DevParams &P, const uint8_t *seq, const 
     return hipGetLastError();
 }
 
+// the four (WINDOWED, EXT) variants of one <C, LPR, RPC> shape
+template <int C, int LPR, int RPC, class... Args>
+static hipError_t launch_trim_lds_variant(const bool windowed, const bool ext, const Args &...args)
+{
+    return ext ? (windowed ? launch_trim_lds<C, true, true, LPR, RPC>(args...) : launch_trim_lds<C, false, true, LPR, RPC>(args...))
+               : (windowed ? launch_trim_lds<C, true, false, LPR, RPC>(args...) : launch_trim_lds<C, false, false, LPR, RPC>(args...));
+}
+
 // Returns hipErrorNotSupported when the configuration is not one trim_lds is compiled for (the caller then takes the
 // other trim kernels).
 hipError_t faqcs_launch_trim_lds(const DevParams &P, const uint8_t *seq, const uint8_t *qual, const uint32_t *off,
@@ -1592,40 +1600,24 @@ hipError_t faqcs_launch_trim_lds(const DevParams &P, const uint8_t *seq, const u
     // every option set except --replace_to_N_q (its G -> N edit needs base and quality of a position together) and the ablation bits
     const bool ext = !plain && P.replace_q == 0 && P.dbg == 0;
     if (!plain && !ext) return hipErrorNotSupported;
-#define FAQCS_LDS_ARGS P, seq, qual, off, n_reads, ad_sl, ad_hit, out, rec_pre, rec_post, counters, err, n_cu, st, tn_flags
-#define FAQCS_LDS_CASE(C)                                                                                                 \
-    return ext ? (windowed ? launch_trim_lds<C, true, true>(FAQCS_LDS_ARGS) : launch_trim_lds<C, false, true>(FAQCS_LDS_ARGS)) \
-               : (windowed ? launch_trim_lds<C, true, false>(FAQCS_LDS_ARGS) : launch_trim_lds<C, false, false>(FAQCS_LDS_ARGS))
-    // measured on MI355X (kernel-only, G reads/s, trim_lds vs trim_tpr): 2x100 7.46 vs 7.10 (C = 13), 2x125 5.64 vs 5.06 on the
-    // C = 19 grid (4.44 on C = 16, whose 128-dword rows put every read of a half wave on the same banks), 2x150 5.8 vs 5.2;
-    // (rounds 2-3: 153..160 bases and every multiple of 32 stayed on trim_tpr -- 8 waves with 160-wide slots; 2x128 at 3.2 G reads/s
-    // here against 5.0 there, every lane of a lane-per-read pass on one LDS bank.  Round 4: 16 lanes per read with smaller chunks
-    // from 153 bases on, padded rows for equal-length chunks of a multiple of 32 bases: 2x128 8.3, 2x155 5.2)
-    // 4 lanes per read: reads of up to 76 bases (2x50, 2x75) -- sixteen reads per step of the position-parallel passes; FAQCS_TRIM_LDS4=0 leaves
-    // them to trim_tpr as in rounds 1-3
-    static const bool lds4_on = [] { const char *e = getenv("FAQCS_TRIM_LDS4"); return !e || atoi(e) != 0; }();
-    if (lds4_on && max_len > 0 && max_len <= 52)
-        return ext ? (windowed ? launch_trim_lds<13, true, true, 4>(FAQCS_LDS_ARGS) : launch_trim_lds<13, false, true, 4>(FAQCS_LDS_ARGS))
-                   : (windowed ? launch_trim_lds<13, true, false, 4>(FAQCS_LDS_ARGS) : launch_trim_lds<13, false, false, 4>(FAQCS_LDS_ARGS));
-    if (lds4_on && max_len > 52 && max_len <= 76)
-        return ext ? (windowed ? launch_trim_lds<19, true, true, 4>(FAQCS_LDS_ARGS) : launch_trim_lds<19, false, true, 4>(FAQCS_LDS_ARGS))
-                   : (windowed ? launch_trim_lds<19, true, false, 4>(FAQCS_LDS_ARGS) : launch_trim_lds<19, false, false, 4>(FAQCS_LDS_ARGS));
-    if (max_len > 76 && max_len <= 104) FAQCS_LDS_CASE(13);  // 2x100
-    if (max_len > 104 && max_len <= 152) FAQCS_LDS_CASE(19); // 2x125, 2x150
-#undef FAQCS_LDS_CASE
-    // 16 lanes per read: 153 ... 252 bases (2x250, 2x251); FAQCS_TRIM_LDS16=0 switches it off (A/B against trim_filter_accumulate)
-    static const bool lds16_on = [] { const char *e = getenv("FAQCS_TRIM_LDS16"); return !e || atoi(e) != 0; }();
-    if (lds16_on && max_len > 152 && max_len <= (uint32_t)lds_maxlen(16, 16))
-        return ext ? (windowed ? launch_trim_lds<16, true, true, 16, FAQCS_LDS16_RPC>(FAQCS_LDS_ARGS) : launch_trim_lds<16, false, true, 16, FAQCS_LDS16_RPC>(FAQCS_LDS_ARGS))
-                   : (windowed ? launch_trim_lds<16, true, false, 16, FAQCS_LDS16_RPC>(FAQCS_LDS_ARGS) : launch_trim_lds<16, false, false, 16, FAQCS_LDS16_RPC>(FAQCS_LDS_ARGS));
-    // 253 ... 304 bases (2x300, 2x301): 16 lanes x 19 positions, chunks of 20 reads (6 KB slots: 12 waves beside a [42][352] quality matrix)
+    // 253 ... 304 bases: the composition records are the two-word ones when the batch holds a read past 256 bases
     DevParams Pw = P;
     Pw.wide_records = max_len > 256 ? 1u : 0u;
-#undef FAQCS_LDS_ARGS
-#define FAQCS_LDS_ARGS Pw, seq, qual, off, n_reads, ad_sl, ad_hit, out, rec_pre, rec_post, counters, err, n_cu, st, tn_flags
-    if (lds16_on && max_len > (uint32_t)lds_maxlen(16, 16) && max_len <= (uint32_t)lds_maxlen(19, 16))
-        return ext ? (windowed ? launch_trim_lds<19, true, true, 16, 20>(FAQCS_LDS_ARGS) : launch_trim_lds<19, false, true, 16, 20>(FAQCS_LDS_ARGS))
-                   : (windowed ? launch_trim_lds<19, true, false, 16, 20>(FAQCS_LDS_ARGS) : launch_trim_lds<19, false, false, 16, 20>(FAQCS_LDS_ARGS));
+    // FAQCS_TRIM_LDS4=0 leaves reads of up to 76 bases to trim_filter_accumulate, FAQCS_TRIM_LDS16=0 those of 153 ... 304 (A/B runs)
+    static const bool lds4_on = [] { const char *e = getenv("FAQCS_TRIM_LDS4"); return !e || atoi(e) != 0; }();
+    static const bool lds16_on = [] { const char *e = getenv("FAQCS_TRIM_LDS16"); return !e || atoi(e) != 0; }();
+    // longest read of the batch -> <C, LPR, RPC>.  C = 19 takes 2x125 as well: C = 16's 128-dword rows put every read of a half wave on the same
+    // banks (4.44 against 5.64 G reads/s).  From 153 bases on: 16 lanes per read with smaller chunks; equal-length chunks of a multiple of 32 bases
+    // are staged as padded rows (every lane of a lane-per-read pass would meet on one LDS bank otherwise).  The measurements behind this table:
+    // DESIGN_HISTORY.md.
+    constexpr uint32_t L16 = lds_maxlen(16, 16), L19 = lds_maxlen(19, 16); // 252, 304
+#define FAQCS_LDS_ARGS(P) windowed, ext, P, seq, qual, off, n_reads, ad_sl, ad_hit, out, rec_pre, rec_post, counters, err, n_cu, st, tn_flags
+    if (lds4_on && max_len > 0 && max_len <= 52) return launch_trim_lds_variant<13, 4, 64>(FAQCS_LDS_ARGS(P));   //   1 ... 52    4 lanes per read: sixteen reads per step of the position-parallel passes (2x50)
+    if (lds4_on && max_len > 52 && max_len <= 76) return launch_trim_lds_variant<19, 4, 64>(FAQCS_LDS_ARGS(P));  //  53 ... 76    (2x75)
+    if (max_len > 76 && max_len <= 104) return launch_trim_lds_variant<13, 8, 64>(FAQCS_LDS_ARGS(P));            //  77 ... 104   8 lanes per read (2x100)
+    if (max_len > 104 && max_len <= 152) return launch_trim_lds_variant<19, 8, 64>(FAQCS_LDS_ARGS(P));           // 105 ... 152   (2x125, 2x150)
+    if (lds16_on && max_len > 152 && max_len <= L16) return launch_trim_lds_variant<16, 16, FAQCS_LDS16_RPC>(FAQCS_LDS_ARGS(P)); // 153 ... 252   16 lanes per read (2x250, 2x251)
+    if (lds16_on && max_len > L16 && max_len <= L19) return launch_trim_lds_variant<19, 16, 20>(FAQCS_LDS_ARGS(Pw)); // 253 ... 304   16 lanes x 19 positions, chunks of 20 reads (2x300, 2x301: 6 KB slots, 12 waves beside a [42][352] quality matrix)
 #undef FAQCS_LDS_ARGS
     return hipErrorNotSupported;
 }

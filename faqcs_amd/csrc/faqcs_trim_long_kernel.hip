@@ -35,7 +35,6 @@ __device__ __forceinline__ uint32_t base_col(const uint32_t b)
     return l == 'a' ? 0u : l == 't' ? 1u : l == 'c' ? 2u : l == 'g' ? 3u : l == 'n' ? 4u : 5u;
 }
 __device__ __forceinline__ void add64(uint64_t *p, const uint64_t v) { atomicAdd(reinterpret_cast<unsigned long long *>(p), (unsigned long long)v); }
-__device__ __forceinline__ uint32_t popc64(const uint64_t m) { return (uint32_t)__builtin_popcountll(m); }
 
 // the six composition bins of one read (trim.cpp:860-874)
 __device__ __forceinline__ void composition_bins(uint64_t *comp, const uint32_t len, const uint32_t nA, const uint32_t nT, const uint32_t nC,

@@ -345,7 +345,7 @@ int  faqcs_debug_words(faqcs_ctx *ctx, uint64_t *out, uint32_t n);
 /* average duration (ms) of the dominant kernel over the launches since the last call, measured with
  * HIP events recorded on the compute stream around each launch */
 int  faqcs_kernel_time_ms(faqcs_ctx *ctx, double *avg_ms, uint64_t *n_launches);
-/* the same per kernel: the trim kernel (and which variant ran: "trim_lds", "trim_tpr", "trim_filter_accumulate") and the
+/* the same per kernel: the trim kernel (and which variant ran: "trim_lds", "trim_filter_accumulate", "trim_long") and the
  * adapter pre-pass adapter_overlap (0 without adapters; a library of several target groups: all its launches); both measured with HIP events on the compute stream */
 typedef struct faqcs_kernel_times {
     double trim_ms, adapter_ms; uint64_t n_launches; const char *trim_kernel;

@@ -284,21 +284,22 @@ def test_every_kernel_width_matches_oracle(args, kind, maxlen):
 @pytest.mark.parametrize("kind,maxlen", [("adv", 150), ("ragged", 100), ("adv", 70), ("adv", 250), ("ragged", 251), ("adv", 300)])
 def test_quality_offsets_that_leave_scores_outside_the_valid_range(in_off, kind, maxlen):
     """Raw quality bytes are generated for Phred+33; decoding them with a larger offset makes most scores negative (clamped to
-    0 by the trimmers, not by the averages) -- the per-position exact pass of the two-phase kernel instead of its four-bytes-per-
-    instruction sums.  Offsets above 86 switch the packed range check off altogether."""
+    0 by the trimmers, not by the averages).  Every length here runs trim_lds (4, 8 and 16 lanes per read, the 304-base variant included): its flat
+    range check over the staged slot finds a byte outside [offset, offset + 41], so the lane-per-read sums run instead of being left to Q-B; they
+    flag the read, whose staged bytes are clamped in place, and the out-of-line exact_quality pass over the arena supplies its sums and the
+    "above 41" verdict instead of the four-bytes-per-instruction sums.  Offsets above 86 (90, 100) switch the packed range check off altogether:
+    every read takes the exact pass."""
     rng = np.random.Generator(np.random.PCG64([11, in_off, maxlen, SEED]))
     opt = parse_args(["-u", "x", "-d", "y", "--ascii", str(in_off), "--min_L", "20"])
     compare_engines(opt, random_batch(rng, 1200, maxlen, kind), R=256 if maxlen <= 256 else 1024, in_off=in_off, seg_size=500)
 
 
-@pytest.mark.parametrize("switch", ["tpr_off", "lds_off"])
-def test_single_pass_kernel_variants_still_match_oracle(switch):
+def test_single_pass_kernel_variants_still_match_oracle():
     """Reads of up to 304 bases run trim_lds.  FAQCS_TRIM_LDS=0 (read once per process) sends the same batches through the single-pass kernel
-    trim_filter_accumulate -- what --replace_to_N_q and reads of 305 ... 1 024 bases use.  (Round 1's two-phase trim_tpr is compiled in only with
-    -DFAQCS_WITH_TRIM_TPR since round 6; in such a build the first of the two runs goes through it, FAQCS_TRIM_TPR=0 switches it off again.)"""
+    trim_filter_accumulate -- what --replace_to_N_q and reads of 305 ... 1 024 bases use."""
     import subprocess
     import sys
-    env = dict(os.environ, FAQCS_TRIM_LDS="0", **({"FAQCS_TRIM_TPR": "0"} if switch == "tpr_off" else {}))
+    env = dict(os.environ, FAQCS_TRIM_LDS="0")
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider",
                         "-k", "test_every_kernel_width_matches_oracle or test_edge_reads or test_quality_error_is_reported"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900)
