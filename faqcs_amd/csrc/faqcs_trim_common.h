@@ -90,6 +90,16 @@ __device__ __forceinline__ void lds_add_u32(uint32_t byte_offset, uint32_t v)
 {
     __hip_atomic_fetch_add((lds_u32_mut)(size_t)byte_offset, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
+// The same add as one line of assembly, for the LDS adds a wave makes WHILE ONE OF ITS LDS-DMA LOADS IS IN FLIGHT (trim_lds: the epilogue under
+// the next chunk's quality DMA, the work under the base DMA).  The compiler cannot tell an LDS store or atomic from the DMA's own write to LDS and
+// puts an s_waitcnt vmcnt(0) in front of the first one it sees behind a DMA, which drains the very load the work was placed under; an
+// instruction inside asm it does not look at.  Nothing comes back, so there is no result to wait for; the adds of a wave reach LDS in issue
+// order like every DS instruction, and the callers wait lgkmcnt(0) before a barrier hands the cells to other waves.
+__device__ __forceinline__ void lds_add_u32_quiet(uint32_t byte_offset, uint32_t v)
+{
+    asm volatile("ds_add_u32 %0, %1" : : "v"(byte_offset), "v"(v) : "memory");
+}
+__device__ __forceinline__ void lds_add_u32_quiet(uint32_t *cell, uint32_t v) { lds_add_u32_quiet((uint32_t)(size_t)(lds_u32_mut)cell, v); }
 template <int C, int J> struct BaseLookup {
     static __device__ __forceinline__ void run(const uint32_t t_base_lds, const uint32_t *ws, uint32_t two, uint32_t *inc)
     {
@@ -242,15 +252,48 @@ __device__ __forceinline__ void fs_acc_flush(FsAcc &f, const int lane, uint32_t 
     const uint32_t s_qt = (uint32_t)wave_sum_i32((int)f.qt);
     const uint32_t s_nn = 0, s_lc = 0, s_avg = 0;
     if (lane == 0) {
-        if (s_tot) { atomicAdd(&lfs[FAQCS_TOTAL_COUNT], s_tot >> 20); atomicAdd(&lfs[FAQCS_TOTAL_NUMBER], s_tot >> 20); atomicAdd(&lfs[FAQCS_TOTAL_LENGTH], s_tot & m); }
-        if (s_trim) { atomicAdd(&lfs[FAQCS_TOTAL_TRIMMED_NUMBER], s_trim >> 20); atomicAdd(&lfs[FAQCS_TOTAL_TRIMMED_LENGTH], s_trim & m); }
-        if (s_len) { atomicAdd(&lfs[FAQCS_READ_LENGTH], s_len >> 20); atomicAdd(&lfs[FAQCS_BASE_LENGTH], s_len & m); }
-        if (s_nn) { atomicAdd(&lfs[FAQCS_READ_NN], s_nn >> 20); atomicAdd(&lfs[FAQCS_BASE_NN], s_nn & m); }
-        if (s_avg) { atomicAdd(&lfs[FAQCS_READ_AVG_Q], s_avg >> 20); atomicAdd(&lfs[FAQCS_BASE_AVG_Q], s_avg & m); }
-        if (s_qt) { atomicAdd(&lfs[FAQCS_READ_QUAL_TRIM], s_qt >> 20); atomicAdd(&lfs[FAQCS_BASE_QUAL_TRIM], s_qt & m); }
-        if (s_lc) { atomicAdd(&lfs[FAQCS_READ_LOW_COMPLEXITY], s_lc >> 20); atomicAdd(&lfs[FAQCS_BASE_LOW_COMPLEXITY], s_lc & m); }
+        if (s_tot) { lds_add_u32_quiet(&lfs[FAQCS_TOTAL_COUNT], s_tot >> 20); lds_add_u32_quiet(&lfs[FAQCS_TOTAL_NUMBER], s_tot >> 20); lds_add_u32_quiet(&lfs[FAQCS_TOTAL_LENGTH], s_tot & m); }
+        if (s_trim) { lds_add_u32_quiet(&lfs[FAQCS_TOTAL_TRIMMED_NUMBER], s_trim >> 20); lds_add_u32_quiet(&lfs[FAQCS_TOTAL_TRIMMED_LENGTH], s_trim & m); }
+        if (s_len) { lds_add_u32_quiet(&lfs[FAQCS_READ_LENGTH], s_len >> 20); lds_add_u32_quiet(&lfs[FAQCS_BASE_LENGTH], s_len & m); }
+        if (s_nn) { lds_add_u32_quiet(&lfs[FAQCS_READ_NN], s_nn >> 20); lds_add_u32_quiet(&lfs[FAQCS_BASE_NN], s_nn & m); }
+        if (s_avg) { lds_add_u32_quiet(&lfs[FAQCS_READ_AVG_Q], s_avg >> 20); lds_add_u32_quiet(&lfs[FAQCS_BASE_AVG_Q], s_avg & m); }
+        if (s_qt) { lds_add_u32_quiet(&lfs[FAQCS_READ_QUAL_TRIM], s_qt >> 20); lds_add_u32_quiet(&lfs[FAQCS_BASE_QUAL_TRIM], s_qt & m); }
+        if (s_lc) { lds_add_u32_quiet(&lfs[FAQCS_READ_LOW_COMPLEXITY], s_lc >> 20); lds_add_u32_quiet(&lfs[FAQCS_BASE_LOW_COMPLEXITY], s_lc & m); }
     }
     f = FsAcc();
+}
+
+// (trim_lds) The half of the deferred epilogue that depends on nothing but the read's length and its pre-trim quality sum: the pre-trim
+// histogram cells and the FilterStat total.  A function of its own so that trim_lds can run it before the bases of the chunk are in LDS, while
+// their DMA is in flight (the LDS adds: lds_add_u32_quiet above); chunk_epilogue calls it itself unless it is told that the caller has (pre_done).
+// The lanes that share the first lane's (length, quality bin) pair are folded into ONE add per cell by that lane: 64 reads of one length are 64
+// adds to one LDS address otherwise, which the LDS serialises (~110 clocks per instruction, measured; equal-length reads with a narrow quality
+// spread are the common case).
+__device__ __forceinline__ void chunk_epilogue_pre(const bool mine, const bool e_err, const uint32_t e_len, const int Vpre, const int lane, uint32_t *hlen,
+                                                   uint32_t *hrq, uint32_t *hbqpre, const uint32_t *t_magic, FsAcc *defer)
+{
+        int qb_pre = 0;
+        if (mine && e_len > 0 && Vpre > 0) qb_pre = e_len == 1 ? Vpre : (int)__umulhi((uint32_t)Vpre, t_magic[e_len]);
+        qb_pre = qb_pre > 41 ? 41 : qb_pre;
+        const bool act = mine && !e_err;
+        if (act) {
+            const uint32_t key = e_len | ((uint32_t)qb_pre << 16);
+            const bool same = key == (uint32_t)__builtin_amdgcn_readfirstlane((int)key);
+            const uint32_t cnt = (uint32_t)__builtin_popcountll(__ballot(same));
+            if (same) {
+                if (lane == __ffsll((unsigned long long)__ballot(true)) - 1) {
+                    lds_add_u32_quiet(hlen + e_len, cnt);
+                    lds_add_u32_quiet(hrq + qb_pre, cnt);
+                    if (e_len) lds_add_u32_quiet(hbqpre + qb_pre, cnt * e_len);
+                }
+            } else {
+                lds_add_u32_quiet(hlen + e_len, 1u);
+                lds_add_u32_quiet(hrq + qb_pre, 1u);
+                if (e_len) lds_add_u32_quiet(hbqpre + qb_pre, e_len);
+            }
+        }
+        const uint32_t one = 1u << 20;
+        defer->tot += mine ? one | e_len : 0u;
 }
 
 template <int LPR>
@@ -258,51 +301,35 @@ __device__ __forceinline__ void chunk_epilogue(const ReadOutcome &o, const bool 
                                                const uint32_t v_hit, const int lane, uint32_t *hlen, uint32_t *hrq, uint32_t *hbqpre,
                                                uint32_t *hbqpost, uint32_t *lfs, const uint32_t *t_magic, uint2 *__restrict__ out,
                                                unsigned long long *__restrict__ rec_pre, unsigned long long *__restrict__ rec_post,
-                                               const bool o_avgq_on, const uint32_t o_dbg, FsAcc *defer = nullptr, const bool wide_rt = false)
+                                               const bool o_avgq_on, const uint32_t o_dbg, FsAcc *defer = nullptr, const bool wide_rt = false,
+                                               const bool pre_done = false)
 {
         const bool e_ret = (o.fl & FAQCS_F_VALID) != 0, e_err = (o.fl & FAQCS_F_ERR_QUALITY) != 0;
         const uint32_t e_len = v_len, e_n = o.an >> 16, e_filt = (o.fl & FAQCS_F_FILTER_MASK) >> FAQCS_F_FILTER_SHIFT;
         // int(ave_Q) == max(0, floor(V / len)), V = sum(raw - offset); floor via mulhi with a host magic
         int qb_pre = 0, qb_post = 0;
-        if (mine && e_len > 0 && o.Vpre > 0) qb_pre = e_len == 1 ? o.Vpre : (int)__umulhi((uint32_t)o.Vpre, t_magic[e_len]);
+        if (!defer && mine && e_len > 0 && o.Vpre > 0) qb_pre = e_len == 1 ? o.Vpre : (int)__umulhi((uint32_t)o.Vpre, t_magic[e_len]);
         if (e_ret && o.Vpost > 0) qb_post = e_n == 1 ? o.Vpost : (int)__umulhi((uint32_t)o.Vpost, t_magic[e_n]);
         qb_pre = qb_pre > 41 ? 41 : qb_pre;
         qb_post = qb_post > 41 ? 41 : qb_post;
         if (defer) {
-            // (trim_lds) the same six histogram cells, with the lanes that share the first lane's (length, quality bin) pair folded
-            // into ONE add per cell by that lane: 64 reads of one length are 64 adds to one LDS address otherwise, which the LDS
-            // serialises (~110 clocks per instruction, measured; equal-length reads with a narrow quality spread are the common case)
+            // (trim_lds) the same six histogram cells, equal ones of a chunk combined: the pre-trim three in chunk_epilogue_pre, here the post-trim three
+            if (!pre_done) chunk_epilogue_pre(mine, e_err, e_len, o.Vpre, lane, hlen, hrq, hbqpre, t_magic, defer);
             const bool act = mine && !e_err;
-            if (act) {
-                const uint32_t key = e_len | ((uint32_t)qb_pre << 16);
-                const bool same = key == (uint32_t)__builtin_amdgcn_readfirstlane((int)key);
-                const uint32_t cnt = (uint32_t)__builtin_popcountll(__ballot(same));
-                if (same) {
-                    if (lane == __ffsll((unsigned long long)__ballot(true)) - 1) {
-                        atomicAdd(hlen + e_len, cnt);
-                        atomicAdd(hrq + qb_pre, cnt);
-                        if (e_len) atomicAdd(hbqpre + qb_pre, cnt * e_len);
-                    }
-                } else {
-                    atomicAdd(hlen + e_len, 1u);
-                    atomicAdd(hrq + qb_pre, 1u);
-                    if (e_len) atomicAdd(hbqpre + qb_pre, e_len);
-                }
-            }
             if (act && e_ret) {
                 const uint32_t key = e_n | ((uint32_t)qb_post << 16);
                 const bool same = key == (uint32_t)__builtin_amdgcn_readfirstlane((int)key);
                 const uint32_t cnt = (uint32_t)__builtin_popcountll(__ballot(same));
                 if (same) {
                     if (lane == __ffsll((unsigned long long)__ballot(true)) - 1) {
-                        atomicAdd(hlen + e_n, cnt << 16);
-                        atomicAdd(hrq + qb_post, cnt << 16);
-                        atomicAdd(hbqpost + qb_post, cnt * e_n);
+                        lds_add_u32_quiet(hlen + e_n, cnt << 16);
+                        lds_add_u32_quiet(hrq + qb_post, cnt << 16);
+                        lds_add_u32_quiet(hbqpost + qb_post, cnt * e_n);
                     }
                 } else {
-                    atomicAdd(hlen + e_n, 0x10000u);
-                    atomicAdd(hrq + qb_post, 0x10000u);
-                    atomicAdd(hbqpost + qb_post, e_n);
+                    lds_add_u32_quiet(hlen + e_n, 0x10000u);
+                    lds_add_u32_quiet(hrq + qb_post, 0x10000u);
+                    lds_add_u32_quiet(hbqpost + qb_post, e_n);
                 }
             }
         } else if (!(o_dbg & 2u) && mine && !e_err) { // length and int(average quality) histograms (trim.cpp:254-258,539-543,877-885)
@@ -336,16 +363,15 @@ __device__ __forceinline__ void chunk_epilogue(const ReadOutcome &o, const bool 
         const bool e_rlen = e_filt == FAQCS_FILT_LENGTH_PRE || e_filt == FAQCS_FILT_LENGTH_POST;
         const uint32_t one = 1u << 20;
         if (defer) { // (a compile-time choice: the pointer is a constant of the inlined call)
-            defer->tot += mine ? one | e_len : 0u;
-            defer->trim += e_ret ? one | e_n : 0u;
+            defer->trim += e_ret ? one | e_n : 0u; // (->tot: chunk_epilogue_pre)
             defer->len += e_rlen ? one | e_n : 0u;
             defer->qt += (o.fl & FAQCS_F_QUAL_TRIMMED) ? one | (o.fl >> 20) : 0u;
             // the rare ones at once (a wave reduction only in a chunk that has such a read)
             const uint32_t m = one - 1u;
             const bool is_nn = (o.fl & FAQCS_F_POLY_N_SEEN) != 0, is_lc = e_filt == FAQCS_FILT_LOW_COMPLEXITY, is_avg = o_avgq_on && e_filt == FAQCS_FILT_AVG_Q;
-            if (__any(is_nn)) { const uint32_t v = (uint32_t)wave_sum_i32((int)(is_nn ? one | e_n : 0u)); if (lane == 0) { atomicAdd(&lfs[FAQCS_READ_NN], v >> 20); atomicAdd(&lfs[FAQCS_BASE_NN], v & m); } }
-            if (__any(is_lc)) { const uint32_t v = (uint32_t)wave_sum_i32((int)(is_lc ? one | e_n : 0u)); if (lane == 0) { atomicAdd(&lfs[FAQCS_READ_LOW_COMPLEXITY], v >> 20); atomicAdd(&lfs[FAQCS_BASE_LOW_COMPLEXITY], v & m); } }
-            if (__any(is_avg)) { const uint32_t v = (uint32_t)wave_sum_i32((int)(is_avg ? one | e_n : 0u)); if (lane == 0) { atomicAdd(&lfs[FAQCS_READ_AVG_Q], v >> 20); atomicAdd(&lfs[FAQCS_BASE_AVG_Q], v & m); } }
+            if (__any(is_nn)) { const uint32_t v = (uint32_t)wave_sum_i32((int)(is_nn ? one | e_n : 0u)); if (lane == 0) { lds_add_u32_quiet(&lfs[FAQCS_READ_NN], v >> 20); lds_add_u32_quiet(&lfs[FAQCS_BASE_NN], v & m); } }
+            if (__any(is_lc)) { const uint32_t v = (uint32_t)wave_sum_i32((int)(is_lc ? one | e_n : 0u)); if (lane == 0) { lds_add_u32_quiet(&lfs[FAQCS_READ_LOW_COMPLEXITY], v >> 20); lds_add_u32_quiet(&lfs[FAQCS_BASE_LOW_COMPLEXITY], v & m); } }
+            if (__any(is_avg)) { const uint32_t v = (uint32_t)wave_sum_i32((int)(is_avg ? one | e_n : 0u)); if (lane == 0) { lds_add_u32_quiet(&lfs[FAQCS_READ_AVG_Q], v >> 20); lds_add_u32_quiet(&lfs[FAQCS_BASE_AVG_Q], v & m); } }
             return;
         }
         const uint32_t s_tot = (uint32_t)wave_sum_i32((int)(mine ? one | e_len : 0u));
@@ -384,9 +410,16 @@ __device__ __forceinline__ void comp_fold_tail(uint32_t *tab, const DevParams &P
     float *normt = reinterpret_cast<float *>(tab + ND);
     uint32_t *s_next = tab + ND + 512;
     const uint32_t n = P.fold_n, n_chunks = (n + CHUNK - 1) / CHUNK;
-    // nothing left in either array: no table to set up
-    if (uniu(__hip_atomic_load(&P.fold_claim[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) >= n_chunks &&
-        uniu(__hip_atomic_load(&P.fold_claim[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) >= n_chunks) return;
+    // nothing left in either array: no table to set up.  ONE thread looks at the two counters and the block takes its verdict from LDS:
+    // the counters move while the waves of a block load them, and a wave that returned alone would leave its siblings at the barriers
+    // below, reading an *s_next nobody wrote
+    if (tid == 0)
+        *s_next = (__hip_atomic_load(&P.fold_claim[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= n_chunks &&
+                   __hip_atomic_load(&P.fold_claim[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= n_chunks) ? 1u : 0u;
+    __syncthreads();
+    const bool nothing_left = *s_next != 0u; // (block-uniform)
+    __syncthreads();                         // (*s_next is written again by the claims below)
+    if (nothing_left) return;
     for (int i = tid; i < ND; i += NT) tab[i] = 0;
     for (int i = tid; i < 512; i += NT) normt[i] = i <= FAQCS_TAB_LEN ? P.comp_norm[i] : 0.0f;
     __syncthreads();

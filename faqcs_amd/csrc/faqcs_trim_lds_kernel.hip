@@ -38,8 +38,8 @@
 //
 // Work distribution: blocks claim GROUPS of NW consecutive chunks from a global counter, waves claim chunks of the block's groups
 // from an LDS counter (a 4-entry ring of group ids), so a block that falls behind simply takes fewer chunks -- the static
-// chunk -> wave map of round 2 ended every launch with a tail of idle CUs.  The offsets / DMA of a wave's NEXT chunk are issued
-// under the epilogue of the current one.  Every FLUSH_CHUNKS chunks the block adds its LDS accumulators to ITS row of a partial-sum
+// chunk -> wave map of round 2 ended every launch with a tail of idle CUs.  The offsets and terminal-N flags of a wave's NEXT chunk are
+// fetched at the top of the current one and stay in flight behind a counted wait; its quality DMA is issued under the epilogue of the current one.  Every FLUSH_CHUNKS chunks the block adds its LDS accumulators to ITS row of a partial-sum
 // array in global memory (plain adds, no atomics: the row is private to the block) and fold_partials, launched behind the kernel,
 // adds the rows to the u64 counter block.
 //
@@ -553,7 +553,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void trim_lds(
     uint32_t bpre[C], bpost[C];
 #pragma unroll
     for (int j = 0; j < C; ++j) { bpre[j] = 0; bpost[j] = 0; }
-    uint32_t any_err = 0;
+    uint32_t any_err = 0; // bit 0: a read of this lane had a quality out of range; bits 1..: the next chunk's terminal-N flags, parked across the S loop
     // the register fields -> the block's position x base cells.  Straight-line: one LDS add per field, no test per lane (the
     // branchy form -- skip a zero field -- cost 23 000 clocks per call: 95 divergent regions with an LDS round trip each)
     FsAcc fs_acc; // FilterStat sums of the chunks since the last spill (7 chunks x 64 reads x 152 bases per wave: inside the packed fields)
@@ -578,11 +578,12 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void trim_lds(
 #pragma unroll
             for (int c = 0; c < FAQCS_NBASE; ++c) {
                 const uint32_t v = ((x >> sh_c[c]) & 63u) | (((y >> sh_c[c]) & 63u) << 16);
-                lds_add_u32(ad_c[c] + (uint32_t)(j * 4), v);
+                lds_add_u32_quiet(ad_c[c] + (uint32_t)(j * 4), v); // (quiet: the due spill of a chunk runs under the chunk's base DMA)
             }
             bpre[j] = 0; bpost[j] = 0;
         }
         fs_acc_flush(fs_acc, lane, smem + Cfg::O_FS);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // (the adds are in the cells before a block flush's barrier is reached)
     };
 
     // ---- the position-parallel passes (8 lanes per read).  What a lane fetches from LDS for one read: six aligned dwords
@@ -825,26 +826,30 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void trim_lds(
 #else
 #define FAQCS_STAMP(i)
 #endif
-    uint32_t p_off = 0, p_end = 0;
-    auto fetch_offsets = [&](const uint32_t chunk_) { // (a chunk past the last one of the launch: a chunk of no reads)
+    // What a chunk needs a whole chunk before its first pass: the lane's two offsets and, when the batch has terminal-N flags, the flags byte
+    // of the lane's read.  EXACTLY N_FETCH = 2 (3 with flags) vector loads, every one of them unconditional: the top of the chunk loop
+    // leaves them in flight behind a counted wait (below), and the count is this number.
+    uint32_t p_off = 0, p_end = 0, p_tn = 0;
+    auto fetch_offsets = [&](const uint32_t chunk_) { // (a chunk past the last one of the launch: a chunk of no reads, nothing is loaded)
         if (chunk_ != NO_CHUNK) {
             // (a lane that owns no read sits at the end of the chunk's last read, with length 0)
             const uint32_t lim_ = umin_(chunk_ * RPC + RPC, n_reads), my_ = owner ? chunk_ * RPC + ridx : lim_;
             p_off = off[my_ < lim_ ? my_ : lim_];
             p_end = off[my_ < lim_ ? my_ + 1 : lim_];
+            if (tn_flags) p_tn = (uint32_t)tn_flags[my_ < lim_ ? my_ : lim_ - 1u]; // (a lane without a read: some read's byte, never looked at)
         }
     };
     // What a chunk needs from global memory before its first pass: the quality span (DMA into the wave's slot), the adapter pre-pass's
     // words, the first / last base of every read (mask_quality_terminal_N looks at them before the qualities are used).
-    struct ChunkLoads { uint32_t v_off, v_end, v_sl, v_hit, pad_len; }; // pad_len (wave-uniform): 0, or the length all reads of the chunk have (padded rows)
-    ChunkLoads ld = {0, 0, 0, 0, 0};
+    struct ChunkLoads { uint32_t v_off, v_end, v_sl, v_hit, pad_len, tn; }; // pad_len (wave-uniform): 0, or the length all reads of the chunk have (padded rows); tn: the read's terminal-N flags
+    ChunkLoads ld = {0, 0, 0, 0, 0, 0};
     // one arena's bytes of the chunk -> the wave's slot: the contiguous span, or one padded row per read (dma_rows)
     auto stage = [&](const uint8_t *arena, const uint32_t cs_, const uint32_t ce_, const uint32_t sh_, const uint32_t pad_len_) {
         if (pad_len_) dma_rows<NI>(arena + cs_ - sh_, pad_len_, (uint32_t)RPC, slot, lane);
         else dma_span<NI>(arena + cs_ - sh_, ce_ - cs_ + sh_, slot, lane);
     };
     bool pre_issued = false;
-    auto issue_loads = [&](const uint32_t chunk_, const uint32_t o_, const uint32_t e_, ChunkLoads &L) {
+    auto issue_loads = [&](const uint32_t chunk_, const uint32_t o_, const uint32_t e_, const uint32_t tn_, ChunkLoads &L) {
         const uint32_t my_ = chunk_ * RPC + ridx;
         const bool mine_ = owner && my_ < n_reads;
         const uint32_t len_ = e_ - o_;
@@ -856,7 +861,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void trim_lds(
         const bool rows_ = (len0_ & 31u) == 0u && len0_ != 0u && len0_ <= (uint32_t)T::PADLEN && __all(!owner || (mine_ && len_ == len0_));
         L.pad_len = rows_ ? len0_ : 0u;
         stage(qual, cs_, ce_, shq_, L.pad_len);
-        L.v_off = o_; L.v_end = e_;
+        L.v_off = o_; L.v_end = e_; L.tn = tn_;
         L.v_sl = (WINDOWED && ad_sl && mine_) ? ad_sl[my_] : (len_ << 16);
         L.v_hit = (ad_hit && mine_) ? ad_hit[my_] : 0u;
     };
@@ -904,7 +909,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void trim_lds(
             const bool mine = owner && my < n_reads;
             // ---- the span of the QUALITY arena -> LDS, and the per-read words that come from global memory.  Requested at the end
             // of the previous chunk (issue_loads below, once the slot is no longer read); here for a wave's first chunk only.
-            if (!pre_issued) issue_loads(chunk_cur, p_off, p_end, ld);
+            if (!pre_issued) issue_loads(chunk_cur, p_off, p_end, p_tn, ld);
             // a lane without a read sits at the end of the last read (length 0): the span ends where lane 63 ends
             const uint32_t v_off = ld.v_off, v_end = ld.v_end;
             const uint32_t v_len = v_end - v_off;
@@ -920,15 +925,37 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void trim_lds(
             // first / last base (mask_quality_terminal_N needs them before the qualities are looked at).  Requested HERE, not with the
             // early loads: a sector of the base arena touched a whole chunk ahead of the base DMA has left the L2 by then and comes
             // over the fabric twice (+100 B/read of fetches, measured)
-            uint32_t bfirst = 0, blast = 0;
-#ifndef FAQCS_LDS_NO_TERMINAL_LOADS // (diagnostic build: what these two scattered loads cost in fabric requests)
-            if (tn_flags) { // the submitter's per-read flags (faqcs_batch::terminal_n): one coalesced byte per read instead
-                const uint32_t f = mine ? (uint32_t)tn_flags[my] : 0u;
-                bfirst = (f & 1u) ? (uint32_t)'N' : 0u; blast = (f & 2u) ? (uint32_t)'N' : 0u;
-            } else if (len) { bfirst = (uint32_t)seq[(size_t)v_off]; blast = (uint32_t)seq[(size_t)v_off + len - 1]; }
+            // Whether the read starts / ends with an upper-case N, and the offsets (and flags) of the wave's NEXT chunk.  Two paths that meet only
+            // behind their waits -- where they met earlier, the compiler made the path with flags wait for the other path's two byte loads:
+            bool n_first = false, n_last = false;
+            if (tn_flags) {
+                // the submitter's per-read flags (faqcs_batch::terminal_n): one coalesced byte per read, which came with the chunk's offsets a
+                // chunk ago (fetch_offsets) -- loaded here, that byte was a global round trip every chunk waited out.
+                const uint32_t f = mine ? ld.tn : 0u;
+                n_first = (f & 1u) != 0u; n_last = (f & 2u) != 0u;
+                fetch_offsets(chunk_next);
+                // Wait for everything OLDER than the loads fetch_offsets has just issued -- the quality DMA, the previous epilogue's stores, the
+                // group counter's atomic -- and leave those in flight: they are not needed before the end of the chunk.  vmcnt counts the
+                // vector memory instructions of a wave that have not completed, loads, stores, atomics and LDS-DMA alike, and on gfx9 they
+                // complete in issue order for this counter (LLVM's AMDGPU memory model: "vector memory operations ... completion is reported
+                // to a wavefront in execution order"; only FLAT instructions that reach LDS are excepted, and there are none here), so "at
+                // most 3 outstanding" retires all but the youngest three: the loads of fetch_offsets (none for a chunk past the last one).
+#ifdef FAQCS_LDS_DIAG_WAIT_ALL_AT_TOP // (diagnostic build: what leaving the three loads in flight returns -- the flags byte still comes a chunk early)
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#else
+                if (chunk_next == NO_CHUNK) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                else asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
 #endif
-            fetch_offsets(chunk_next);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            } else {
+                uint32_t bfirst = 0, blast = 0;
+#ifndef FAQCS_LDS_NO_TERMINAL_LOADS // (diagnostic build: what these two scattered loads cost in fabric requests)
+                if (len) { bfirst = (uint32_t)seq[(size_t)v_off]; blast = (uint32_t)seq[(size_t)v_off + len - 1]; }
+#endif
+                fetch_offsets(chunk_next);
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // (the two bytes are needed at once: one round trip for the four loads, as ever)
+                asm volatile("" : "+v"(bfirst), "+v"(blast));    // (looked at on THIS path)
+                n_first = bfirst == 'N'; n_last = blast == 'N';
+            }
             if (at_group_start) { // publish group number L + 1 of the block, or the block's chunk count when the launch has no group left
                 const uint32_t L1 = c_next / NW + 1u, gid = fetch_group ? gridDim.x + uniu(g_new) : n_groups;
                 if (lane == 0) {
@@ -949,15 +976,15 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void trim_lds(
             ReadOutcome oc;
             uint32_t v_patch = (uint32_t)len << 16; // lead | trail << 16
             // ---- mask_quality_terminal_N (trim.cpp:1191-1216): upper-case 'N' runs at either end get Q0, in place ----
-            const bool tn = len > 0 && (bfirst == 'N' || blast == 'N');
+            const bool tn = len > 0 && (n_first || n_last);
             if (__any(tn)) {
                 int lead = 0, trail = len;
-                bool go = tn && bfirst == 'N';
+                bool go = tn && n_first;
 #pragma unroll 1
                 while (__any(go)) {
                     if (go) { ++lead; go = lead < len && seq[(size_t)v_off + lead] == 'N'; }
                 }
-                go = tn && blast == 'N' && lead < len;
+                go = tn && n_last && lead < len;
                 if (tn && lead >= len) trail = 0;
 #pragma unroll 1
                 while (__any(go)) {
@@ -1253,10 +1280,15 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void trim_lds(
             const uint32_t shs = (uint32_t)((size_t)(seq + cs) & 15u);
             stage(seq, cs, ce, shs, pad_len);
             const uint32_t rows = pad_len ? ridx * pad_stride + shs : v_off - cs + shs;
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             FAQCS_STAMP(5)
-
-            // ================= S: 8 lanes per read, the bases (base_step) ==============================================
+#ifdef FAQCS_LDS_DIAG_NO_WORK_UNDER_DMA // (diagnostic build: the same work behind the wait -- what placing it under the DMA returns)
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#endif
+            // ---- under the base DMA: what needs neither the slot nor the bases.  The pre-trim half of the epilogue (the read's length and
+            // V_pre are final), the register spill when one is due (accumulator cells and registers only), the words the S loop is handed.
+            // Nothing here writes to a slot, and every LDS add is a quiet one (faqcs_trim_common.h): the compiler would drain the DMA in front of any other.
+            chunk_epilogue_pre(mine, read_err, v_len, V_pre, lane, smem + Cfg::O_LEN, smem + Cfg::O_RQ, smem + Cfg::O_BQPRE, smem + Cfg::O_TMAGIC, &fs_acc);
+            if (++since_spill == REG_FLUSH_EVERY) { spill_base_regs(); since_spill = 0; } // (before this chunk's S pass: seven S passes between two spills, as ever)
             // i1: a | n << 8 | post << 16 | counted << 17 | chk << 18.  chk: the read fails the average quality but is still judged for
             // poly-N, which the reference tests first (trim.cpp:363-382).
             const uint32_t si0 = rows | ((uint32_t)len << 16);
@@ -1266,6 +1298,18 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void trim_lds(
             const uint32_t vpk = WIDE ? (uint32_t)V_pre : (((uint32_t)V_pre & 0xffffu) | ((uint32_t)V_post << 16)), vpk2 = WIDE ? (uint32_t)V_post : 0u;
             const uint32_t fpk = flags | (filt << FAQCS_F_FILTER_SHIFT);
             const uint32_t v_hit_w = v_hit;
+#ifdef FAQCS_LDS_STAMPS
+            { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); st_spill += now_ - st_prev; st_prev = now_; } // (the work under the DMA: counted with the spills)
+#endif
+            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); // the bases are in the slot (and the next chunk's offsets and flags in their registers)
+            // (the compiler does not read the wait above.  Shown the three registers here, it puts a wait of its own at this spot, where nothing is
+            // in flight; left to find out later, it drains the next chunk's quality DMA in front of the register copies at the end of the loop)
+            asm volatile("" : "+v"(p_off), "+v"(p_end), "+v"(p_tn));
+            // the next chunk's flags byte goes into spare bits of any_err for the S loop, the kernel's register peak: no register of its own there
+            any_err |= p_tn << 1;
+            FAQCS_STAMP(5)
+
+            // ================= S: 8 lanes per read, the bases (base_step) ==============================================
 #define FAQCS_S_LOOP(I1, MODE)                                                                                        \
     {                                                                                                                 \
         _Pragma("unroll 1") for (int t = 0; t < TPR; ++t) {                                                          \
@@ -1475,7 +1519,8 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void trim_lds(
             // fetched at the top of this chunk)
             ChunkLoads ld_next = ld;
             pre_issued = chunk_next != NO_CHUNK;
-            if (pre_issued) issue_loads(chunk_next, p_off, p_end, ld_next);
+            if (pre_issued) issue_loads(chunk_next, p_off, p_end, any_err >> 1, ld_next);
+            any_err &= 1u;
 
             if (read_err) { any_err = 1; flags |= FAQCS_F_ERR_QUALITY; }
             oc.an = (uint32_t)a | ((uint32_t)n << 16);
@@ -1488,19 +1533,15 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void trim_lds(
             // ---- chunk epilogue: one read per lane ----------------------------------------------------------
             chunk_epilogue<LPR>(oc, mine, my, v_len, v_hit, lane, smem + Cfg::O_LEN, smem + Cfg::O_RQ, smem + Cfg::O_BQPRE,
                                 smem + Cfg::O_BQPOST, smem + Cfg::O_FS, smem + Cfg::O_TMAGIC, out, rec_pre, rec_post, EXT && P.avgq_on != 0, 0u, &fs_acc,
-                                WIDE && P.wide_records != 0u); // (a batch with a read past 256 bases: the two-word records composition_histogram then expects)
+                                WIDE && P.wide_records != 0u, true); // (the pre-trim half: done under the base DMA; a batch with a read past 256 bases: the two-word records composition_histogram then expects)
             ld = ld_next;
             }
         }
 
         FAQCS_STAMP(8)
-        if (++since_spill == REG_FLUSH_EVERY) { spill_base_regs(); since_spill = 0; }
-#ifdef FAQCS_LDS_STAMPS
-        st_spill += __builtin_amdgcn_s_memtime() - st_prev; // (the register spill: outside the nine sections, like the block flush)
-#endif
         c_cur = c_next; chunk_cur = chunk_next;
     }
-    if (__any(any_err != 0) && lane == 0) atomicOr(err, 1u);
+    if (__any((any_err & 1u) != 0) && lane == 0) atomicOr(err, 1u);
     if (tid == 0) P.partial_rows[blockIdx.x] = n_flushed; // rows of P.partials this block wrote (fold_partials)
     // ---- the block has run out of reads: its LDS (every wave has passed the last flush) folds composition records of the PREVIOUS launch
     // while the slowest blocks of this one finish (round 6; faqcs_trim_common.h: comp_fold_tail)

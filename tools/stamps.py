@@ -39,3 +39,6 @@ tot = float(w[:9].sum())
 for i, nm in enumerate(names):
     print("%-26s %7.1f clocks/read-chunk-wave = %5.1f %%" % (nm, w[i] / (3 * n / 64), 100.0 * w[i] / tot))
 print("total %.0f clocks per 64-read chunk per wave" % (tot / (3 * n / 64)))
+# outside the nine sections (load S counts the DMA's issue and the wait for it, not the work placed between the two)
+print("%-26s %7.1f clocks/read-chunk-wave" % ("block flushes (+ barrier)", w[11] / (3 * n / 64)))
+print("%-26s %7.1f clocks/read-chunk-wave" % ("work under the base DMA", w[12] / (3 * n / 64)))
