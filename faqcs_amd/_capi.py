@@ -14,6 +14,7 @@ NCOMP_KIND = 6
 SEGMENT_READS = 32768
 MAX_READ_LENGTH = 32767       # FAQCS_MAX_READ_LENGTH: longest read the library takes (batches with a read > 1 024 bases run on trim_long)
 FAST_READ_LENGTH = 1024       # longest read of the chunked kernels
+ARENA_PAD_BEFORE, ARENA_PAD_AFTER = 16, 64  # FAQCS_ARENA_PAD_*: readable bytes in front of / behind a device-resident batch's arenas
 
 (TOTAL_COUNT, TOTAL_NUMBER, TOTAL_LENGTH, TOTAL_TRIMMED_NUMBER, TOTAL_TRIMMED_LENGTH, PAIRED_READ_NUMBER,
  PAIRED_BASE_LENGTH, READ_LENGTH, BASE_LENGTH, READ_NN, BASE_NN, READ_PHIX, BASE_PHIX, READ_ADAPTER,
@@ -53,6 +54,17 @@ class Batch(C.Structure):
         ("n_segments", C.c_uint32), ("segment_start", C.c_void_p), ("max_read_len", C.c_uint32),
         ("terminal_n", C.c_void_p),  # optional per-read flags (faqcs_submit_device only); None = the kernels look themselves
     ]
+
+
+class EmitInfo(C.Structure):
+    """faqcs_emit_info: what an emission needs (always) and whether it fitted."""
+    _fields_ = [("n_bytes", C.c_uint64), ("n_reads", C.c_uint32), ("overflow", C.c_uint32)]
+
+
+class EmitOut(C.Structure):
+    """faqcs_emit_out: device pointers of the caller's output arenas (faqcs_emit_device)."""
+    _fields_ = [("seq", C.c_void_p), ("qual", C.c_void_p), ("capacity_bytes", C.c_uint64), ("offset", C.c_void_p),
+                ("index", C.c_void_p), ("info", C.c_void_p)]
 
 
 class Layout(C.Structure):
@@ -145,6 +157,7 @@ def load_library():
         "faqcs_submit": (i32, [vp, C.POINTER(Batch), vp]),
         "faqcs_submit_device": (i32, [vp, C.POINTER(Batch), vp]),
         "faqcs_sync": (i32, [vp]),
+        "faqcs_emit_device": (i32, [vp, C.POINTER(Batch), vp, vp, C.POINTER(EmitOut)]),
         "faqcs_submit_async": (i32, [vp, C.POINTER(Batch), vp, C.POINTER(u64)]),
         "faqcs_wait": (i32, [vp, u64]),
         "faqcs_host_alloc": (vp, [C.c_size_t]),
@@ -177,6 +190,7 @@ def load_library():
         "faqcs_synth_fill": (i32, [i32, vp, vp, vp, u32, u32, u64, u64, C.c_float]),
         "faqcs_synth_fill_genome": (i32, [i32, vp, vp, vp, u32, u32, u64, u64, u64]),
         "faqcs_terminal_n_flags": (i32, [i32, vp, vp, u32, vp]),
+        "faqcs_emit_time_ms": (i32, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "faqcs_kernel_time_ms": (i32, [vp, C.POINTER(C.c_double), C.POINTER(u64)]),
         "faqcs_debug_words": (i32, [vp, vp, u32]),
         "faqcs_kernel_report": (i32, [vp, C.POINTER(KernelTimes)]),

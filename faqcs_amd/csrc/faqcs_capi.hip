@@ -46,6 +46,12 @@ hipError_t faqcs_launch_adapter(const AdapterDev &A, const AdapterGroup *G, cons
 hipError_t faqcs_launch_synth(uint8_t *d_seq, uint8_t *d_qual, uint32_t *d_offset, uint32_t n_reads, uint32_t L,
                               uint64_t seed, uint64_t first_read, float adapter_frac, uint64_t genome_len, float at_frac, hipStream_t st);
 
+size_t faqcs_emit_scratch_bytes(uint32_t n_reads);
+hipError_t faqcs_launch_emit_scan(const uint8_t *seq, const uint32_t *off, const uint8_t *tn, uint32_t n_reads, const faqcs_read_result *res,
+                                  const uint8_t *keep, const faqcs_emit_out *out, void *scratch, hipStream_t st);
+hipError_t faqcs_launch_emit_gather(const uint8_t *seq, const uint8_t *qual, uint32_t n_reads, const faqcs_emit_out *out, const void *scratch,
+                                    int in_off, int out_off, uint32_t replace_q, int n_cu, hipStream_t st);
+
 static thread_local std::string g_err;
 static int fail(int code, const std::string &msg) { g_err = msg; return code; }
 #define HIPCHK(x)                                                                                         \
@@ -114,6 +120,9 @@ struct faqcs_ctx {
     DevBuf<uint32_t> s_seg, s_sl;
     DevBuf<uint16_t> s_hit;
     DevBuf<faqcs_read_result> s_res;
+    DevBuf<uint4> s_emit; // faqcs_emit_device: the scan's tile sums and the 16-byte record of every emitted read
+    hipEvent_t emit_ev[3] = {nullptr, nullptr, nullptr}; // around the scan and the gather of the last emission (faqcs_emit_time_ms)
+    bool emit_timed = false;
     // per-read composition records (trim kernel -> composition_histogram).  Two sets: the histogram kernels of
     // submission k run on the aux stream next to the trim kernel of submission k+1 (LDS-bound next to VALU-bound).
     struct RecSet { DevBuf<unsigned long long> pre, post; hipEvent_t trimmed = nullptr, folded = nullptr; bool used = false; };
@@ -498,6 +507,7 @@ extern "C" void faqcs_destroy(faqcs_ctx *c)
     for (auto &t : c->timings) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); (void)hipEventDestroy(t.p); (void)hipEventDestroy(t.k0); (void)hipEventDestroy(t.k1); }
     if (c->comm) comm_release(c->comm);
     if (c->comm_ev) (void)hipEventDestroy(c->comm_ev);
+    for (auto &e : c->emit_ev) if (e) (void)hipEventDestroy(e);
     if (c->ins_a) (void)hipEventDestroy(c->ins_a);
     if (c->ins_b) (void)hipEventDestroy(c->ins_b);
     for (int k = 0; k < 2; ++k) { if (c->fwd_free[k]) (void)hipEventDestroy(c->fwd_free[k]); if (c->fwd_copied[k]) (void)hipEventDestroy(c->fwd_copied[k]); c->fwd_items[k].release(); }
@@ -506,7 +516,7 @@ extern "C" void faqcs_destroy(faqcs_ctx *c)
     for (void *q : ptrs) if (q) (void)hipFree(q);
     for (auto &sl : c->slot) { sl.seq.release(); sl.qual.release(); sl.tn.release(); sl.off.release(); if (sl.done) (void)hipEventDestroy(sl.done); }
     for (auto &e : c->ticket_ev) if (e) (void)hipEventDestroy(e);
-    c->s_seg.release(); c->s_sl.release(); c->s_hit.release(); c->s_res.release(); c->s_astate.release(); c->s_amask.release();
+    c->s_seg.release(); c->s_sl.release(); c->s_hit.release(); c->s_res.release(); c->s_emit.release(); c->s_astate.release(); c->s_amask.release();
     for (auto &rs : c->rec) { rs.pre.release(); rs.post.release(); if (rs.trimmed) (void)hipEventDestroy(rs.trimmed); if (rs.folded) (void)hipEventDestroy(rs.folded); }
     if (c->aux) (void)hipStreamDestroy(c->aux);
     c->ob_items.release(); c->ob_wave_count.release(); c->ob_wave_offset.release();
@@ -1252,6 +1262,42 @@ extern "C" int faqcs_submit_device(faqcs_ctx *c, const faqcs_batch *b, faqcs_rea
     if (max_len > FAQCS_MAX_READ_LENGTH) return fail(FAQCS_E_INVAL, "faqcs_submit_device: reads longer than FAQCS_MAX_READ_LENGTH bases are not supported by the HIP kernels");
     if (!d_results) { HIPCHK(c->s_res.reserve((size_t)n + 1)); d_results = c->s_res.p; }
     return enqueue(c, b->seq, b->qual, b->offset, n, max_len, b->segment_start, b->n_segments, d_results, b->terminal_n);
+}
+
+extern "C" int faqcs_emit_device(faqcs_ctx *c, const faqcs_batch *b, const faqcs_read_result *d_results, const uint8_t *d_keep, const faqcs_emit_out *out)
+{
+    if (!c) return fail(FAQCS_E_INVAL, "null ctx");
+    if (!b || !d_results || !out) return fail(FAQCS_E_INVAL, "faqcs_emit_device: null batch, results or output");
+    if (!out->seq || !out->qual || !out->offset || !out->info) return fail(FAQCS_E_INVAL, "faqcs_emit_device: null output arena, offset or info");
+    if (((uintptr_t)out->seq | (uintptr_t)out->qual) & 15u) return fail(FAQCS_E_INVAL, "faqcs_emit_device: the output arenas must be 16-byte aligned");
+    const uint32_t n = b->n_reads;
+    if (n && (!b->seq || !b->qual || !b->offset)) return fail(FAQCS_E_INVAL, "faqcs_emit_device: null batch arrays");
+    HIPCHK(hipSetDevice(c->device));
+    const size_t need = (faqcs_emit_scratch_bytes(n) + sizeof(uint4) - 1) / sizeof(uint4);
+    if (need > c->s_emit.cap) HIPCHK(hipStreamSynchronize(c->compute)); // (growing frees the scratch an earlier emission may still read)
+    HIPCHK(c->s_emit.reserve(need));
+    for (auto &e : c->emit_ev) if (!e) HIPCHK(hipEventCreate(&e));
+    HIPCHK(hipEventRecord(c->emit_ev[0], c->compute));
+    HIPCHK(faqcs_launch_emit_scan(b->seq, b->offset, b->terminal_n, n, d_results, d_keep, out, c->s_emit.p, c->compute));
+    HIPCHK(hipEventRecord(c->emit_ev[1], c->compute));
+    HIPCHK(faqcs_launch_emit_gather(b->seq, b->qual, n, out, c->s_emit.p, c->prm.input_quality_offset, c->prm.output_quality_offset,
+                                    c->prm.replace_to_N_q, c->n_cu, c->compute));
+    HIPCHK(hipEventRecord(c->emit_ev[2], c->compute));
+    c->emit_timed = true;
+    return 0;
+}
+
+extern "C" int faqcs_emit_time_ms(faqcs_ctx *c, double *scan_ms, double *gather_ms)
+{
+    if (!c || !scan_ms || !gather_ms) return fail(FAQCS_E_INVAL, "null argument");
+    if (!c->emit_timed) return fail(FAQCS_E_INVAL, "faqcs_emit_time_ms: no emission on this context yet");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipEventSynchronize(c->emit_ev[2]));
+    float a = 0.f, g = 0.f;
+    HIPCHK(hipEventElapsedTime(&a, c->emit_ev[0], c->emit_ev[1]));
+    HIPCHK(hipEventElapsedTime(&g, c->emit_ev[1], c->emit_ev[2]));
+    *scan_ms = a; *gather_ms = g;
+    return 0;
 }
 
 extern "C" int faqcs_terminal_n_flags(int device_id, const uint8_t *d_seq, const uint32_t *d_offset, uint32_t n_reads, uint8_t *d_flags)

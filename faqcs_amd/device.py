@@ -1,0 +1,44 @@
+"""Torch-facing helpers of the device seam: inputs and outputs are torch tensors that live on the GPU; the work is the
+library's HIP kernels (faqcs_emit_device), never torch ops."""
+import ctypes as C
+
+from . import _capi as capi
+from .engine import FaqcsError
+
+
+def trimmed_reads(engine, seq, qual, offset, results, keep=None, terminal_n=None):
+    """The trimmed, edited reads of a device-resident batch, packed back to back on the device.
+
+    seq / qual: uint8 CUDA tensors whose element 0 is the batch's byte 0 (padding contract of faqcs_batch: 16 readable bytes in
+    front, 64 behind -- pass a view into a larger tensor); offset: int32 / uint32 tensor [n + 1]; results: the (n, 4) int16 tensor
+    faqcs_submit_device() filled on `engine`; keep: optional uint8 / bool tensor [n] (0 = do not emit); terminal_n: optional uint8
+    tensor [n] (faqcs_batch.terminal_n).  Returns (seq, qual, offset, index): uint8 [n_bytes] x 2, int32 [n_emitted + 1] (bit
+    pattern of uint32), int32 [n_emitted] (input index of every emitted read).  The returned seq / qual are views that start
+    16-byte aligned, 64 bytes into their storage, with 64 spare bytes behind: a valid input batch for faqcs_submit_device()."""
+    import torch
+
+    n = int(offset.numel()) - 1
+    dev = seq.device
+    cap = int(seq.numel())  # an emission never exceeds the input bytes
+    front = 64
+    o_seq = torch.empty(front + cap + capi.ARENA_PAD_AFTER + 16, dtype=torch.uint8, device=dev)
+    o_qual = torch.empty_like(o_seq)
+    o_off = torch.empty(n + 1, dtype=torch.int32, device=dev)
+    o_idx = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    info = torch.zeros(2, dtype=torch.int64, device=dev)
+    shift = [(-(t.data_ptr() + front)) % 16 for t in (o_seq, o_qual)]
+    if keep is not None:
+        keep = keep.to(torch.uint8).contiguous()
+    batch = capi.Batch(seq.data_ptr(), qual.data_ptr(), offset.data_ptr(), n, 0, None, 0,
+                       terminal_n.data_ptr() if terminal_n is not None and n else None)
+    out = capi.EmitOut(o_seq.data_ptr() + front + shift[0], o_qual.data_ptr() + front + shift[1], cap, o_off.data_ptr(),
+                       o_idx.data_ptr(), info.data_ptr())
+    torch.cuda.current_stream(dev).synchronize()  # the library's compute stream is its own: the inputs must be complete
+    engine.emit_device(batch, results.data_ptr(), out, keep.data_ptr() if keep is not None and n else None)
+    engine.sync()
+    h = info.cpu().numpy()
+    n_bytes, n_emit, overflow = int(h[0]), int(h[1]) & 0xFFFFFFFF, int(h[1]) >> 32
+    if overflow:
+        raise FaqcsError(capi.E_INVAL, "faqcs_emit_device: the emission needs %d bytes, the output arenas hold %d" % (n_bytes, cap))
+    a, b = front + shift[0], front + shift[1]
+    return o_seq[a:a + n_bytes], o_qual[b:b + n_bytes], o_off[:n_emit + 1], o_idx[:n_emit]

@@ -152,6 +152,28 @@ def edited_arenas(opt, in_off, seq, qual, offset):
     return s, q
 
 
+def emit_model(opt, in_off, seq, qual, offset, res, keep=None):
+    """What faqcs_emit_device() packs, as numpy: every read with F_VALID (and keep[i] != 0 when keep is given), in input order, its
+    kept window cut out of edited_arenas().  -> (seq, qual, offset uint32[n_emitted + 1], index uint32[n_emitted])"""
+    offset = np.asarray(offset)
+    n = len(offset) - 1
+    sel = (res["flags"][:n] & capi.F_VALID) != 0
+    if keep is not None:
+        sel &= np.asarray(keep)[:n] != 0
+    index = np.nonzero(sel)[0].astype(np.uint32)
+    lens = res["len"][index].astype(np.int64)
+    out_off = np.zeros(len(index) + 1, dtype=np.int64)
+    out_off[1:] = np.cumsum(lens)
+    total = int(out_off[-1])
+    if total == 0:
+        z = np.zeros(0, dtype=np.uint8)
+        return z, z.copy(), out_off.astype(np.uint32), index
+    es, eq = edited_arenas(opt, in_off, seq, qual, offset)
+    first = offset[index].astype(np.int64) + res["start"][index].astype(np.int64)
+    src = np.repeat(first - out_off[:-1], lens) + np.arange(total, dtype=np.int64)
+    return es[src], eq[src], out_off.astype(np.uint32), index
+
+
 class Run:
     """State the reference keeps in main(): filter_stats, adapter_stats, PlotInfo, Options (FaQCs.cpp:67-69)."""
 

@@ -57,6 +57,17 @@ class HipEngine:
         _check(self.lib, self.lib.faqcs_sync(self.ctx))
         return res
 
+    def emit_device(self, batch, d_results, out, d_keep=None):
+        """faqcs_emit_device: packs the trimmed, edited reads of a device-resident batch (a capi.Batch of device pointers, as given to
+        faqcs_submit_device, and its device results) into the arenas of `out` (a capi.EmitOut).  Enqueued; sync() waits."""
+        _check(self.lib, self.lib.faqcs_emit_device(self.ctx, C.byref(batch), d_results, d_keep, C.byref(out)))
+
+    def emit_time_ms(self):
+        """(scan ms, gather ms) of the last emit_device() on this engine (HIP events on the compute stream); waits for it."""
+        a, g = C.c_double(), C.c_double()
+        _check(self.lib, self.lib.faqcs_emit_time_ms(self.ctx, C.byref(a), C.byref(g)))
+        return a.value, g.value
+
     def set_quality(self, q):
         _check(self.lib, self.lib.faqcs_set_quality(self.ctx, int(q)))
 

@@ -31,7 +31,8 @@ extern "C" {
  * every existing structure and call as it was, so the number stands: faqcs_kmer_forward, faqcs_comm_* (round 4).  Round 5 changes what the
  * 16-byte items of the k-mer exchange MEAN (faqcs_kmer_outbox / _insert_device / _forward: opaque to every caller in this repository, which
  * only moves them) -- a run of up to 17 consecutive k-mers each instead of one (key, epoch) pair -- and nothing about their size or the calls.
- * Round 6 adds faqcs_kmer_finish_pass, and faqcs_sync() no longer counts the k-mers that wait in the open group (see below). */
+ * Round 6 adds faqcs_kmer_finish_pass, and faqcs_sync() no longer counts the k-mers that wait in the open group (see below).
+ * faqcs_emit_device (the trimmed, edited reads packed on the device) is a new entry point with structures of its own. */
 #define FAQCS_ABI_VERSION 2
 
 /* FilterStat enum order, FaQCs.h:46-75 */
@@ -215,6 +216,37 @@ int  faqcs_submit_device(faqcs_ctx *ctx, const faqcs_batch *batch, faqcs_read_re
 
 int  faqcs_sync(faqcs_ctx *ctx);
 
+/* The output half of the device seam: the reads themselves.  Packs, on the device, the record the reference would write for every
+ * selected read of a batch that went through faqcs_submit_device() -- the kept window with the byte edits documented at faqcs_read_result,
+ * byte for byte what faqcs_apply_edits() writes on the host -- back to back into two arenas the caller owns.
+ *   batch, d_results  what was given to faqcs_submit_device() (seq / qual / offset / terminal_n are DEVICE pointers; terminal_n, when present,
+ *                     is used; segment_start is not needed and may be NULL).  The call is enqueued on the context's compute stream behind
+ *                     that submission and returns at once; faqcs_sync() waits.
+ *   d_keep            OPTIONAL device array, one byte per read.  Read i is emitted when d_results[i].flags & FAQCS_F_VALID and (d_keep ==
+ *                     NULL or d_keep[i] != 0).  This is how a caller routes pairs the way FaQCs.cpp:296-361 does: valid1 & valid2 for the
+ *                     two paired streams, valid1 ^ valid2 for the unpaired one.
+ *   out               all DEVICE pointers.  Emitted reads keep input order: emitted read k occupies seq / qual [offset[k], offset[k + 1]) and
+ *                     is input read index[k].  info->n_bytes and info->n_reads are ALWAYS the sizes the emission needs.  When n_bytes >
+ *                     capacity_bytes (or >= 2^32: offsets are 32 bits wide, and the emission of a batch never exceeds its input bytes),
+ *                     overflow = 1 and NOTHING is written to seq, qual, offset[1..] or index: no truncation, ever.  Otherwise overflow = 0.
+ *                     The kernel stores whole 16-byte pieces, so bytes [n_bytes, n_bytes rounded up to 16) of seq / qual may be overwritten
+ *                     with unspecified values; nothing else outside [0, n_bytes), offset[0 .. n_reads] and index[0 .. n_reads) is touched.
+ *                     With FAQCS_ARENA_PAD_BEFORE readable bytes left in front of seq / qual by the caller, (seq, qual, offset, n_reads) is
+ *                     thereby a valid input batch for faqcs_submit_device().
+ * Parameters come from the context: input_quality_offset, output_quality_offset, replace_to_N_q.  n_reads == 0 is fine and yields zeros.
+ * FAQCS_E_INVAL: a null ctx / batch / d_results / out / out->seq / qual / offset / info, out->seq or out->qual not 16-byte aligned.  Scan scratch
+ * (16 bytes per read) is the library's: grown on demand, freed by faqcs_destroy(). */
+typedef struct faqcs_emit_info { uint64_t n_bytes; uint32_t n_reads; uint32_t overflow; } faqcs_emit_info;
+typedef struct faqcs_emit_out {
+    uint8_t  *seq, *qual;             /* 16-byte aligned; capacity_bytes + FAQCS_ARENA_PAD_AFTER bytes writable */
+    uint64_t  capacity_bytes;
+    uint32_t *offset;                 /* batch->n_reads + 1 entries; [0] = 0, [k + 1] = end of emitted read k */
+    uint32_t *index;                  /* OPTIONAL, batch->n_reads entries: input index of emitted read k (to gather ids / deflines) */
+    faqcs_emit_info *info;            /* emitted reads, emitted bytes, overflow flag */
+} faqcs_emit_out;
+int  faqcs_emit_device(faqcs_ctx *ctx, const faqcs_batch *batch, const faqcs_read_result *d_results,
+                       const uint8_t *d_keep, const faqcs_emit_out *out);
+
 /* Pipelined form of faqcs_submit(): returns a ticket; faqcs_wait(ticket) blocks until THAT batch's results have
  * landed in `results` (later batches may still be in flight: two input staging slots let the H2D copy of batch
  * k+1 overlap the kernels of batch k).  Host arenas / result arrays obtained from faqcs_host_alloc() are pinned,
@@ -340,6 +372,9 @@ int  faqcs_terminal_n_flags(int device_id, const uint8_t *d_seq, const uint32_t 
  * (either strand, 0.5 % substitutions, the same quality recipe), so distinct k-mers grow as on real data. */
 int  faqcs_synth_fill_genome(int device_id, uint8_t *d_seq, uint8_t *d_qual, uint32_t *d_offset, uint32_t n_reads,
                              uint32_t L, uint64_t seed, uint64_t first_read, uint64_t genome_len);
+/* duration (ms) of the scan and of the gather of the LAST faqcs_emit_device() on the context, measured with HIP events recorded on the
+ * compute stream around them; waits for that emission */
+int  faqcs_emit_time_ms(faqcs_ctx *ctx, double *scan_ms, double *gather_ms);
 /* diagnostic builds only: section clocks accumulated by the trim kernel (16 words; read and cleared) */
 int  faqcs_debug_words(faqcs_ctx *ctx, uint64_t *out, uint32_t n);
 /* average duration (ms) of the dominant kernel over the launches since the last call, measured with
