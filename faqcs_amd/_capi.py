@@ -67,6 +67,22 @@ class EmitOut(C.Structure):
                 ("index", C.c_void_p), ("info", C.c_void_p)]
 
 
+# FAQCS_PARSE_*: faqcs_parse_info.error, the error of record n_reads
+PARSE_OK, PARSE_E_SEQUENCE, PARSE_E_PLUS, PARSE_E_PLUS_DELIM, PARSE_E_QUALITY, PARSE_E_LENGTH = range(6)
+
+
+class ParseInfo(C.Structure):
+    """faqcs_parse_info: what the parsed records need (always), the text they cover, and whether they fitted."""
+    _fields_ = [("n_bytes", C.c_uint64), ("consumed", C.c_uint64), ("n_reads", C.c_uint32), ("max_read_len", C.c_uint32),
+                ("overflow", C.c_uint32), ("error", C.c_int32)]
+
+
+class ParseOut(C.Structure):
+    """faqcs_parse_out: the caller's output arrays (device pointers for faqcs_parse_device, host pointers for faqcs_parse_host)."""
+    _fields_ = [("seq", C.c_void_p), ("qual", C.c_void_p), ("capacity_bytes", C.c_uint64), ("capacity_reads", C.c_uint32),
+                ("offset", C.c_void_p), ("terminal_n", C.c_void_p), ("def_pos", C.c_void_p), ("def_len", C.c_void_p), ("info", C.c_void_p)]
+
+
 class Layout(C.Structure):
     _fields_ = [("max_read_length", C.c_uint32), ("n_adapters", C.c_uint32)] + [
         (n, C.c_uint64) for n in (
@@ -158,6 +174,10 @@ def load_library():
         "faqcs_submit_device": (i32, [vp, C.POINTER(Batch), vp]),
         "faqcs_sync": (i32, [vp]),
         "faqcs_emit_device": (i32, [vp, C.POINTER(Batch), vp, vp, C.POINTER(EmitOut)]),
+        "faqcs_parse_error_text": (C.c_char_p, [i32]),
+        "faqcs_parse_device": (i32, [vp, vp, u64, i32, C.POINTER(ParseOut)]),
+        "faqcs_parse_host": (i32, [vp, u64, i32, C.POINTER(ParseOut)]),
+        "faqcs_parse_time_ms": (i32, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "faqcs_submit_async": (i32, [vp, C.POINTER(Batch), vp, C.POINTER(u64)]),
         "faqcs_wait": (i32, [vp, u64]),
         "faqcs_host_alloc": (vp, [C.c_size_t]),

@@ -52,6 +52,11 @@ hipError_t faqcs_launch_emit_scan(const uint8_t *seq, const uint32_t *off, const
 hipError_t faqcs_launch_emit_gather(const uint8_t *seq, const uint8_t *qual, uint32_t n_reads, const faqcs_emit_out *out, const void *scratch,
                                     int in_off, int out_off, uint32_t replace_q, int n_cu, hipStream_t st);
 
+size_t faqcs_parse_scratch_bytes(unsigned long long n_text);
+hipError_t faqcs_launch_parse_index(const uint8_t *text, unsigned long long n_text, int final, void *scratch, hipStream_t st);
+hipError_t faqcs_launch_parse_records(const uint8_t *text, unsigned long long n_text, const faqcs_parse_out *out, void *scratch, int n_cu, hipStream_t st);
+hipError_t faqcs_launch_parse_gather(const uint8_t *text, unsigned long long n_text, const faqcs_parse_out *out, const void *scratch, int n_cu, hipStream_t st);
+
 static thread_local std::string g_err;
 static int fail(int code, const std::string &msg) { g_err = msg; return code; }
 #define HIPCHK(x)                                                                                         \
@@ -123,6 +128,9 @@ struct faqcs_ctx {
     DevBuf<uint4> s_emit; // faqcs_emit_device: the scan's tile sums and the 16-byte record of every emitted read
     hipEvent_t emit_ev[3] = {nullptr, nullptr, nullptr}; // around the scan and the gather of the last emission (faqcs_emit_time_ms)
     bool emit_timed = false;
+    DevBuf<uint4> s_parse; // faqcs_parse_device: the line index, the record lengths and the two scans' tile sums
+    hipEvent_t parse_ev[3] = {nullptr, nullptr, nullptr}; // around the index + records and the gather of the last parse (faqcs_parse_time_ms)
+    bool parse_timed = false;
     // per-read composition records (trim kernel -> composition_histogram).  Two sets: the histogram kernels of
     // submission k run on the aux stream next to the trim kernel of submission k+1 (LDS-bound next to VALU-bound).
     struct RecSet { DevBuf<unsigned long long> pre, post; hipEvent_t trimmed = nullptr, folded = nullptr; bool used = false; };
@@ -508,6 +516,7 @@ extern "C" void faqcs_destroy(faqcs_ctx *c)
     if (c->comm) comm_release(c->comm);
     if (c->comm_ev) (void)hipEventDestroy(c->comm_ev);
     for (auto &e : c->emit_ev) if (e) (void)hipEventDestroy(e);
+    for (auto &e : c->parse_ev) if (e) (void)hipEventDestroy(e);
     if (c->ins_a) (void)hipEventDestroy(c->ins_a);
     if (c->ins_b) (void)hipEventDestroy(c->ins_b);
     for (int k = 0; k < 2; ++k) { if (c->fwd_free[k]) (void)hipEventDestroy(c->fwd_free[k]); if (c->fwd_copied[k]) (void)hipEventDestroy(c->fwd_copied[k]); c->fwd_items[k].release(); }
@@ -516,7 +525,7 @@ extern "C" void faqcs_destroy(faqcs_ctx *c)
     for (void *q : ptrs) if (q) (void)hipFree(q);
     for (auto &sl : c->slot) { sl.seq.release(); sl.qual.release(); sl.tn.release(); sl.off.release(); if (sl.done) (void)hipEventDestroy(sl.done); }
     for (auto &e : c->ticket_ev) if (e) (void)hipEventDestroy(e);
-    c->s_seg.release(); c->s_sl.release(); c->s_hit.release(); c->s_res.release(); c->s_emit.release(); c->s_astate.release(); c->s_amask.release();
+    c->s_seg.release(); c->s_sl.release(); c->s_hit.release(); c->s_res.release(); c->s_emit.release(); c->s_parse.release(); c->s_astate.release(); c->s_amask.release();
     for (auto &rs : c->rec) { rs.pre.release(); rs.post.release(); if (rs.trimmed) (void)hipEventDestroy(rs.trimmed); if (rs.folded) (void)hipEventDestroy(rs.folded); }
     if (c->aux) (void)hipStreamDestroy(c->aux);
     c->ob_items.release(); c->ob_wave_count.release(); c->ob_wave_offset.release();
@@ -1297,6 +1306,122 @@ extern "C" int faqcs_emit_time_ms(faqcs_ctx *c, double *scan_ms, double *gather_
     HIPCHK(hipEventElapsedTime(&a, c->emit_ev[0], c->emit_ev[1]));
     HIPCHK(hipEventElapsedTime(&g, c->emit_ev[1], c->emit_ev[2]));
     *scan_ms = a; *gather_ms = g;
+    return 0;
+}
+
+static const char *const PARSE_TEXT[] = {"", "fastq.cpp:next_read: Unable to read sequence", "fastq.cpp:next_read: Unable to read '+'",
+                                         "fastq.cpp:next_read: Error reading '+' delimiter", "fastq.cpp:next_read: Unable to read quality",
+                                         "fastq.cpp:next_read: |Sequence| != |Quality|"};
+extern "C" const char *faqcs_parse_error_text(int code) { return code >= 0 && code <= FAQCS_PARSE_E_LENGTH ? PARSE_TEXT[code] : nullptr; }
+
+static int parse_check_args(const char *who, const uint8_t *text, uint64_t n_text, const faqcs_parse_out *out)
+{
+    const std::string w(who);
+    if (!out || (!text && n_text)) return fail(FAQCS_E_INVAL, w + ": null text or output");
+    if (!out->seq || !out->qual || !out->offset || !out->terminal_n || !out->info) return fail(FAQCS_E_INVAL, w + ": null output arena, offset, terminal_n or info");
+    if (((uintptr_t)out->seq | (uintptr_t)out->qual) & 15u) return fail(FAQCS_E_INVAL, w + ": the output arenas must be 16-byte aligned");
+    if ((out->def_pos == nullptr) != (out->def_len == nullptr)) return fail(FAQCS_E_INVAL, w + ": def_pos and def_len go together");
+    if (n_text >= (1ull << 32)) return fail(FAQCS_E_INVAL, w + ": a text of 2^32 bytes or more must be cut into chunks (final = 0, consumed)");
+    return 0;
+}
+
+extern "C" int faqcs_parse_device(faqcs_ctx *c, const uint8_t *d_text, uint64_t n_text, int final, const faqcs_parse_out *out)
+{
+    if (!c) return fail(FAQCS_E_INVAL, "null ctx");
+    if (int rc = parse_check_args("faqcs_parse_device", d_text, n_text, out)) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    const size_t need = (faqcs_parse_scratch_bytes(n_text) + sizeof(uint4) - 1) / sizeof(uint4);
+    if (need > c->s_parse.cap) HIPCHK(hipStreamSynchronize(c->compute)); // (growing frees the scratch an earlier parse may still read)
+    HIPCHK(c->s_parse.reserve(need));
+    for (auto &e : c->parse_ev) if (!e) HIPCHK(hipEventCreate(&e));
+    HIPCHK(hipEventRecord(c->parse_ev[0], c->compute));
+    HIPCHK(faqcs_launch_parse_index(d_text, n_text, final ? 1 : 0, c->s_parse.p, c->compute));
+    HIPCHK(faqcs_launch_parse_records(d_text, n_text, out, c->s_parse.p, c->n_cu, c->compute));
+    HIPCHK(hipEventRecord(c->parse_ev[1], c->compute));
+    HIPCHK(faqcs_launch_parse_gather(d_text, n_text, out, c->s_parse.p, c->n_cu, c->compute));
+    HIPCHK(hipEventRecord(c->parse_ev[2], c->compute));
+    c->parse_timed = true;
+    return 0;
+}
+
+extern "C" int faqcs_parse_time_ms(faqcs_ctx *c, double *index_ms, double *gather_ms)
+{
+    if (!c || !index_ms || !gather_ms) return fail(FAQCS_E_INVAL, "null argument");
+    if (!c->parse_timed) return fail(FAQCS_E_INVAL, "faqcs_parse_time_ms: no parse on this context yet");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipEventSynchronize(c->parse_ev[2]));
+    float a = 0.f, g = 0.f;
+    HIPCHK(hipEventElapsedTime(&a, c->parse_ev[0], c->parse_ev[1]));
+    HIPCHK(hipEventElapsedTime(&g, c->parse_ev[1], c->parse_ev[2]));
+    *index_ms = a; *gather_ms = g;
+    return 0;
+}
+
+// The host statement of the parse rules (include/faqcs_mi.h at faqcs_parse_device).  Two passes over the text: what the records need, then --
+// when it fits -- the records.
+extern "C" int faqcs_parse_host(const uint8_t *text, uint64_t n_text, int final, const faqcs_parse_out *out)
+{
+    if (int rc = parse_check_args("faqcs_parse_host", text, n_text, out)) return rc;
+    // [content end, start of the next line, terminated?] of the line that starts at p
+    auto line = [&](uint64_t p, uint64_t &content_end, uint64_t &next) -> bool {
+        uint64_t x = p;
+        while (x < n_text && text[x] != '\n' && text[x] != '\r') ++x;
+        content_end = x;
+        while (x < n_text && text[x] != '\n') ++x;
+        if (x == n_text) { next = n_text; return false; }
+        next = x + 1;
+        return true;
+    };
+    faqcs_parse_info info{};
+    for (int pass = 0; pass < 2; ++pass) {
+        uint64_t p = 0, o = 0;
+        uint32_t k = 0;
+        if (pass) out->offset[0] = 0;
+        const uint32_t stop = pass ? info.n_reads : 0xffffffffu;
+        while (p < n_text && k < stop) {
+            uint64_t e0, e1, e2, e3, n0, n1, n2, n3;
+            int err = FAQCS_PARSE_OK;
+            bool complete = false; // (final = 0: a record whose lines do not all end in '\n' is not there yet)
+            const bool t0 = line(p, e0, n0);
+            bool t1 = false, t2 = false, t3 = false;
+            if (n0 >= n_text) err = FAQCS_PARSE_E_SEQUENCE;
+            else {
+                t1 = line(n0, e1, n1);
+                if (n1 >= n_text) err = FAQCS_PARSE_E_PLUS;
+                else {
+                    t2 = line(n1, e2, n2);
+                    if (!t2) err = FAQCS_PARSE_E_PLUS_DELIM;
+                    else if (n2 >= n_text) err = FAQCS_PARSE_E_QUALITY;
+                    else {
+                        t3 = line(n2, e3, n3);
+                        complete = true;
+                        if (e1 - n0 != e3 - n2) err = FAQCS_PARSE_E_LENGTH;
+                    }
+                }
+            }
+            if (!final && !(complete && t0 && t1 && t2 && t3)) break; // left to the caller, no error
+            if (err) { info.error = err; break; }
+            const uint64_t len = e1 - n0;
+            if (pass) {
+                memcpy(out->seq + o, text + n0, (size_t)len);
+                memcpy(out->qual + o, text + n2, (size_t)len);
+                out->terminal_n[k] = len ? (uint8_t)((text[n0] == 'N' ? 1 : 0) | (text[n0 + len - 1] == 'N' ? 2 : 0)) : (uint8_t)0;
+                if (out->def_pos) { out->def_pos[k] = (uint32_t)p; out->def_len[k] = (uint32_t)(e0 - p); }
+                out->offset[k + 1] = (uint32_t)(o + len);
+            } else {
+                if (len > info.max_read_len) info.max_read_len = (uint32_t)len;
+                info.consumed = n3;
+            }
+            o += len; ++k;
+            p = n3;
+        }
+        if (pass) break;
+        info.n_bytes = o;
+        info.n_reads = k;
+        info.overflow = (o > out->capacity_bytes || k > out->capacity_reads || o >= (1ull << 32)) ? 1u : 0u;
+        *out->info = info;
+        if (info.overflow) break;
+    }
     return 0;
 }
 

@@ -91,6 +91,49 @@ class FastqReader:
         self.f.close()
 
 
+def parse_model(text: bytes, final: bool):
+    """What faqcs_parse_device() / faqcs_parse_host() deliver, written from the rules of include/faqcs_mi.h (fastq.cpp:8-125) and not
+    from the library: a line ends at '\\n', its content at its first '\\r' (or the '\\n', or the end of the text); a record is four lines;
+    the first record with |bases| != |qualities| or, in a final text, with lines missing decides the error, and the records in front of
+    it are delivered.  A text that is not final delivers only records whose four lines all end in '\\n'.
+    -> (seq, qual, offset uint32[n + 1], terminal_n uint8[n], def_pos uint32[n], def_len uint32[n], consumed, error)"""
+    text = bytes(text)
+    lines = text.split(b"\n")  # n_newlines + 1 pieces; the last one is the unterminated rest (b"" when the text ends in '\n' or is empty)
+    n_nl = len(lines) - 1
+    open_tail = len(lines[-1]) > 0
+    starts = np.zeros(len(lines) + 1, dtype=np.int64)
+    starts[1:] = np.cumsum([len(x) + 1 for x in lines])
+    ltot = n_nl + (1 if open_tail else 0)
+    n_cand = ltot // 4 if final else n_nl // 4
+    tail = capi.PARSE_OK
+    if final:
+        tail = (capi.PARSE_OK, capi.PARSE_E_SEQUENCE, capi.PARSE_E_PLUS,
+                capi.PARSE_E_PLUS_DELIM if open_tail else capi.PARSE_E_QUALITY)[ltot % 4]
+
+    def content(x):
+        i = x.find(b"\r")
+        return x if i < 0 else x[:i]
+
+    seqs, quals, tn, dpos, dlen = [], [], [], [], []
+    error, n = tail, n_cand
+    for k in range(n_cand):
+        d, s, q = content(lines[4 * k]), content(lines[4 * k + 1]), content(lines[4 * k + 3])
+        if len(s) != len(q):
+            error, n = capi.PARSE_E_LENGTH, k
+            break
+        seqs.append(s)
+        quals.append(q)
+        tn.append(((1 if s[:1] == b"N" else 0) | (2 if s[-1:] == b"N" else 0)) if s else 0)
+        dpos.append(int(starts[4 * k]))
+        dlen.append(len(d))
+    consumed = min(int(starts[4 * n]), len(text))  # (a final text's last quality line may lack its '\n')
+    offset = np.zeros(n + 1, dtype=np.uint32)
+    if n:
+        offset[1:] = np.cumsum([len(x) for x in seqs])
+    return (np.frombuffer(b"".join(seqs), dtype=np.uint8), np.frombuffer(b"".join(quals), dtype=np.uint8), offset,
+            np.asarray(tn, dtype=np.uint8), np.asarray(dpos, dtype=np.uint32), np.asarray(dlen, dtype=np.uint32), consumed, error)
+
+
 def pack_segments(buffers):
     """buffers: list of lists of (def, seq, qual).  -> (seq arena, qual arena, offset, segment_start)"""
     lens, seg = [], [0]

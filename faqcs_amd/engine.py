@@ -68,6 +68,17 @@ class HipEngine:
         _check(self.lib, self.lib.faqcs_emit_time_ms(self.ctx, C.byref(a), C.byref(g)))
         return a.value, g.value
 
+    def parse_device(self, d_text, n_text, final, out):
+        """faqcs_parse_device: FASTQ text in device memory (d_text: device address, readable ARENA_PAD_BEFORE bytes in front and
+        ARENA_PAD_AFTER behind) -> the packed batch in the arrays of `out` (a capi.ParseOut of device pointers).  Enqueued; sync() waits."""
+        _check(self.lib, self.lib.faqcs_parse_device(self.ctx, d_text, int(n_text), 1 if final else 0, C.byref(out)))
+
+    def parse_time_ms(self):
+        """(index + records ms, gather ms) of the last parse_device() on this engine (HIP events on the compute stream); waits for it."""
+        a, g = C.c_double(), C.c_double()
+        _check(self.lib, self.lib.faqcs_parse_time_ms(self.ctx, C.byref(a), C.byref(g)))
+        return a.value, g.value
+
     def set_quality(self, q):
         _check(self.lib, self.lib.faqcs_set_quality(self.ctx, int(q)))
 

@@ -32,7 +32,8 @@ extern "C" {
  * 16-byte items of the k-mer exchange MEAN (faqcs_kmer_outbox / _insert_device / _forward: opaque to every caller in this repository, which
  * only moves them) -- a run of up to 17 consecutive k-mers each instead of one (key, epoch) pair -- and nothing about their size or the calls.
  * Round 6 adds faqcs_kmer_finish_pass, and faqcs_sync() no longer counts the k-mers that wait in the open group (see below).
- * faqcs_emit_device (the trimmed, edited reads packed on the device) is a new entry point with structures of its own. */
+ * faqcs_emit_device (the trimmed, edited reads packed on the device) is a new entry point with structures of its own, and so are
+ * faqcs_parse_device / faqcs_parse_host (FASTQ text to a packed batch). */
 #define FAQCS_ABI_VERSION 2
 
 /* FilterStat enum order, FaQCs.h:46-75 */
@@ -247,6 +248,65 @@ typedef struct faqcs_emit_out {
 int  faqcs_emit_device(faqcs_ctx *ctx, const faqcs_batch *batch, const faqcs_read_result *d_results,
                        const uint8_t *d_keep, const faqcs_emit_out *out);
 
+/* The input half of the device seam: FASTQ text -> the packed batch faqcs_submit_device() takes.
+ * The rules are those of the reference's next_read (fastq.cpp:8-125), as the command line's parse_range states them:
+ *   - a LINE ends at '\n'; its CONTENT is [line start, first '\r' or '\n', else end of text).  Bytes between a '\r' and the line's '\n'
+ *     belong to nothing.
+ *   - a record is four lines: defline, bases, plus line, qualities.  The defline is not checked for '@', the plus line's content is not
+ *     looked at.  |bases content| != |quality content| is FAQCS_PARSE_E_LENGTH of that record.
+ *   - final = 1: the text is the end of the input.  With Ltot = the number of '\n', plus 1 if the text does not end in '\n' and is not
+ *     empty, Ltot / 4 records are complete (a last quality line without '\n' is accepted) and Ltot % 4 decides the tail error of record
+ *     Ltot / 4: 1 E_SEQUENCE, 2 E_PLUS, 3 E_PLUS_DELIM when the third line has no '\n' and E_QUALITY when it has.  (A blank line at the
+ *     end of a file is therefore E_SEQUENCE, as in the reference.)
+ *   - final = 0: the text may stop anywhere.  Only records whose four lines all end in '\n' inside the text are parsed, the rest is left
+ *     to the caller (info->consumed is where the next chunk starts) and there is no tail error.
+ *   - errors are sequential: the first bad record in input order decides, info->n_reads is its index, and everything in front of it is
+ *     parsed and delivered as if the text ended there.
+ *   - there is no read-length limit here: info->max_read_len reports, faqcs_submit_device() keeps refusing what it refuses.
+ * faqcs_parse_device: every pointer is a DEVICE pointer (d_text, and every pointer of *out, out->info included).  The call is enqueued on
+ * the context's compute stream and returns at once; faqcs_sync() waits.
+ *   d_text, n_text    the text.  It must be readable FAQCS_ARENA_PAD_BEFORE bytes in front of d_text and FAQCS_ARENA_PAD_AFTER bytes behind
+ *                     d_text + n_text; those bytes are never interpreted.  No alignment is asked of it.  n_text >= 2^32 is FAQCS_E_INVAL at
+ *                     call time: positions are 32 bits wide, and a caller cuts a larger file into chunks (final = 0, consumed).
+ *   out               info is ALWAYS complete: the sizes the parsed records need, the text they cover, the error of record n_reads.  When
+ *                     n_bytes > capacity_bytes, n_reads > capacity_reads or n_bytes >= 2^32, overflow = 1 and NOTHING but info is written:
+ *                     no truncation, ever.  Otherwise the kernels touch only bytes [0, n_bytes rounded up to 16) of seq and qual (whole
+ *                     16-byte pieces are stored), offset[0 .. n_reads], terminal_n[0 .. n_reads) and def_pos / def_len [0 .. n_reads).
+ *                     With FAQCS_ARENA_PAD_BEFORE readable bytes left in front of seq / qual by the caller, (seq, qual, offset, terminal_n,
+ *                     n_reads, max_read_len) is thereby a valid batch for faqcs_submit_device().
+ * n_text == 0 yields zeros and offset[0] = 0.  FAQCS_E_INVAL: a null ctx / d_text (with n_text > 0) / out / out->seq / qual / offset /
+ * terminal_n / info, out->seq or out->qual not 16-byte aligned, exactly one of def_pos and def_len given, n_text >= 2^32.
+ * Scratch is the library's: grown on demand, freed by faqcs_destroy().  The number of lines of a text is known on the device only and the
+ * host does not wait for it, so the scratch is sized by what n_text bytes can hold at most: 5 bytes per byte of text (a line start per
+ * byte, a record length per four bytes).  A caller that minds cuts the text into smaller chunks.
+ * faqcs_parse_host is the same with HOST pointers: the host statement of these rules, plain single-threaded C++ with no HIP call (no
+ * padding is needed around the text, and exactly [0, n_bytes) of the arenas is written). */
+enum { FAQCS_PARSE_OK = 0, FAQCS_PARSE_E_SEQUENCE, FAQCS_PARSE_E_PLUS, FAQCS_PARSE_E_PLUS_DELIM,
+       FAQCS_PARSE_E_QUALITY, FAQCS_PARSE_E_LENGTH };
+const char *faqcs_parse_error_text(int code);   /* the "fastq.cpp:next_read: ..." strings faqcs_mi prints; "" for FAQCS_PARSE_OK, NULL for no code */
+
+typedef struct faqcs_parse_info {
+    uint64_t n_bytes;      /* arena bytes the parsed records need (sum of their base-line contents) */
+    uint64_t consumed;     /* text bytes covered by the parsed records: the next chunk starts here */
+    uint32_t n_reads;      /* records parsed (== index of the bad record when error != 0) */
+    uint32_t max_read_len;
+    uint32_t overflow;     /* 1: n_bytes > capacity_bytes, n_reads > capacity_reads or n_bytes >= 2^32 */
+    int32_t  error;        /* FAQCS_PARSE_* of record n_reads */
+} faqcs_parse_info;
+
+typedef struct faqcs_parse_out {
+    uint8_t  *seq, *qual;          /* 16-byte aligned, capacity_bytes + FAQCS_ARENA_PAD_AFTER writable */
+    uint64_t  capacity_bytes;
+    uint32_t  capacity_reads;
+    uint32_t *offset;              /* capacity_reads + 1 */
+    uint8_t  *terminal_n;          /* capacity_reads; the flags of faqcs_batch.terminal_n */
+    uint32_t *def_pos, *def_len;   /* OPTIONAL (both or neither): defline content of record k = text[def_pos[k] .. +def_len[k]) */
+    faqcs_parse_info *info;
+} faqcs_parse_out;
+
+int  faqcs_parse_device(faqcs_ctx *ctx, const uint8_t *d_text, uint64_t n_text, int final, const faqcs_parse_out *out);
+int  faqcs_parse_host(const uint8_t *text, uint64_t n_text, int final, const faqcs_parse_out *out);
+
 /* Pipelined form of faqcs_submit(): returns a ticket; faqcs_wait(ticket) blocks until THAT batch's results have
  * landed in `results` (later batches may still be in flight: two input staging slots let the H2D copy of batch
  * k+1 overlap the kernels of batch k).  Host arenas / result arrays obtained from faqcs_host_alloc() are pinned,
@@ -375,6 +435,8 @@ int  faqcs_synth_fill_genome(int device_id, uint8_t *d_seq, uint8_t *d_qual, uin
 /* duration (ms) of the scan and of the gather of the LAST faqcs_emit_device() on the context, measured with HIP events recorded on the
  * compute stream around them; waits for that emission */
 int  faqcs_emit_time_ms(faqcs_ctx *ctx, double *scan_ms, double *gather_ms);
+/* the same for the LAST faqcs_parse_device() on the context: the line index and the records (index_ms), the gather (gather_ms) */
+int  faqcs_parse_time_ms(faqcs_ctx *ctx, double *index_ms, double *gather_ms);
 /* diagnostic builds only: section clocks accumulated by the trim kernel (16 words; read and cleared) */
 int  faqcs_debug_words(faqcs_ctx *ctx, uint64_t *out, uint32_t n);
 /* average duration (ms) of the dominant kernel over the launches since the last call, measured with
