@@ -67,6 +67,16 @@ class EmitOut(C.Structure):
                 ("index", C.c_void_p), ("info", C.c_void_p)]
 
 
+class RenderInfo(C.Structure):
+    """faqcs_render_info: what a rendering needs (always) and whether it fitted."""
+    _fields_ = [("n_bytes", C.c_uint64), ("n_reads", C.c_uint32), ("overflow", C.c_uint32)]
+
+
+class RenderOut(C.Structure):
+    """faqcs_render_out: the caller's output arrays (device pointers for faqcs_render_device, host pointers for faqcs_render_host)."""
+    _fields_ = [("text", C.c_void_p), ("capacity_bytes", C.c_uint64), ("rec_offset", C.c_void_p), ("rec_index", C.c_void_p), ("info", C.c_void_p)]
+
+
 # FAQCS_PARSE_*: faqcs_parse_info.error, the error of record n_reads
 PARSE_OK, PARSE_E_SEQUENCE, PARSE_E_PLUS, PARSE_E_PLUS_DELIM, PARSE_E_QUALITY, PARSE_E_LENGTH = range(6)
 
@@ -178,6 +188,9 @@ def load_library():
         "faqcs_parse_device": (i32, [vp, vp, u64, i32, C.POINTER(ParseOut)]),
         "faqcs_parse_host": (i32, [vp, u64, i32, C.POINTER(ParseOut)]),
         "faqcs_parse_time_ms": (i32, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+        "faqcs_render_device": (i32, [vp, C.POINTER(Batch), vp, vp, vp, vp, vp, vp, C.POINTER(RenderOut)]),
+        "faqcs_render_host": (i32, [C.POINTER(Params), C.POINTER(Batch), vp, vp, vp, vp, vp, vp, C.POINTER(RenderOut)]),
+        "faqcs_render_time_ms": (i32, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "faqcs_submit_async": (i32, [vp, C.POINTER(Batch), vp, C.POINTER(u64)]),
         "faqcs_wait": (i32, [vp, u64]),
         "faqcs_host_alloc": (vp, [C.c_size_t]),

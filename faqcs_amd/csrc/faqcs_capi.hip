@@ -57,6 +57,12 @@ hipError_t faqcs_launch_parse_index(const uint8_t *text, unsigned long long n_te
 hipError_t faqcs_launch_parse_records(const uint8_t *text, unsigned long long n_text, const faqcs_parse_out *out, void *scratch, int n_cu, hipStream_t st);
 hipError_t faqcs_launch_parse_gather(const uint8_t *text, unsigned long long n_text, const faqcs_parse_out *out, const void *scratch, int n_cu, hipStream_t st);
 
+size_t faqcs_render_scratch_bytes(uint32_t n_reads);
+hipError_t faqcs_launch_render_scan(const faqcs_batch *b, const faqcs_read_result *res, const uint32_t *def_pos, const uint32_t *def_len,
+                                    const uint8_t *select, const uint32_t *order, const faqcs_render_out *out, void *scratch, hipStream_t st);
+hipError_t faqcs_launch_render_gather(const faqcs_batch *b, bool trimmed, const uint8_t *text, const faqcs_render_out *out, const void *scratch,
+                                      int in_off, int out_off, uint32_t replace_q, int n_cu, hipStream_t st);
+
 static thread_local std::string g_err;
 static int fail(int code, const std::string &msg) { g_err = msg; return code; }
 #define HIPCHK(x)                                                                                         \
@@ -131,6 +137,9 @@ struct faqcs_ctx {
     DevBuf<uint4> s_parse; // faqcs_parse_device: the line index, the record lengths and the two scans' tile sums
     hipEvent_t parse_ev[3] = {nullptr, nullptr, nullptr}; // around the index + records and the gather of the last parse (faqcs_parse_time_ms)
     bool parse_timed = false;
+    DevBuf<uint4> s_render; // faqcs_render_device: the 32-byte descriptor and the text offset of every rendered record, the scan's tile sums
+    hipEvent_t render_ev[3] = {nullptr, nullptr, nullptr}; // around the scan and the gather of the last rendering (faqcs_render_time_ms)
+    bool render_timed = false;
     // per-read composition records (trim kernel -> composition_histogram).  Two sets: the histogram kernels of
     // submission k run on the aux stream next to the trim kernel of submission k+1 (LDS-bound next to VALU-bound).
     struct RecSet { DevBuf<unsigned long long> pre, post; hipEvent_t trimmed = nullptr, folded = nullptr; bool used = false; };
@@ -516,6 +525,7 @@ extern "C" void faqcs_destroy(faqcs_ctx *c)
     if (c->comm) comm_release(c->comm);
     if (c->comm_ev) (void)hipEventDestroy(c->comm_ev);
     for (auto &e : c->emit_ev) if (e) (void)hipEventDestroy(e);
+    for (auto &e : c->render_ev) if (e) (void)hipEventDestroy(e);
     for (auto &e : c->parse_ev) if (e) (void)hipEventDestroy(e);
     if (c->ins_a) (void)hipEventDestroy(c->ins_a);
     if (c->ins_b) (void)hipEventDestroy(c->ins_b);
@@ -525,7 +535,7 @@ extern "C" void faqcs_destroy(faqcs_ctx *c)
     for (void *q : ptrs) if (q) (void)hipFree(q);
     for (auto &sl : c->slot) { sl.seq.release(); sl.qual.release(); sl.tn.release(); sl.off.release(); if (sl.done) (void)hipEventDestroy(sl.done); }
     for (auto &e : c->ticket_ev) if (e) (void)hipEventDestroy(e);
-    c->s_seg.release(); c->s_sl.release(); c->s_hit.release(); c->s_res.release(); c->s_emit.release(); c->s_parse.release(); c->s_astate.release(); c->s_amask.release();
+    c->s_seg.release(); c->s_sl.release(); c->s_hit.release(); c->s_res.release(); c->s_emit.release(); c->s_parse.release(); c->s_render.release(); c->s_astate.release(); c->s_amask.release();
     for (auto &rs : c->rec) { rs.pre.release(); rs.post.release(); if (rs.trimmed) (void)hipEventDestroy(rs.trimmed); if (rs.folded) (void)hipEventDestroy(rs.folded); }
     if (c->aux) (void)hipStreamDestroy(c->aux);
     c->ob_items.release(); c->ob_wave_count.release(); c->ob_wave_offset.release();
@@ -1419,6 +1429,104 @@ extern "C" int faqcs_parse_host(const uint8_t *text, uint64_t n_text, int final,
         info.n_bytes = o;
         info.n_reads = k;
         info.overflow = (o > out->capacity_bytes || k > out->capacity_reads || o >= (1ull << 32)) ? 1u : 0u;
+        *out->info = info;
+        if (info.overflow) break;
+    }
+    return 0;
+}
+
+static int render_check_args(const char *who, const faqcs_batch *b, const uint8_t *text, const uint32_t *def_pos, const uint32_t *def_len, const faqcs_render_out *out)
+{
+    const std::string w(who);
+    if (!b || !out) return fail(FAQCS_E_INVAL, w + ": null batch or output");
+    if (!def_pos || !def_len) return fail(FAQCS_E_INVAL, w + ": null defline spans");
+    if (!out->text || !out->info) return fail(FAQCS_E_INVAL, w + ": null output text or info");
+    if ((uintptr_t)out->text & 15u) return fail(FAQCS_E_INVAL, w + ": the output text must be 16-byte aligned");
+    if (b->n_reads && (!text || !b->seq || !b->qual || !b->offset)) return fail(FAQCS_E_INVAL, w + ": null text or batch arrays");
+    return 0;
+}
+
+extern "C" int faqcs_render_device(faqcs_ctx *c, const faqcs_batch *b, const faqcs_read_result *d_results, const uint8_t *d_text,
+                                   const uint32_t *d_def_pos, const uint32_t *d_def_len, const uint8_t *d_select, const uint32_t *d_order,
+                                   const faqcs_render_out *out)
+{
+    if (!c) return fail(FAQCS_E_INVAL, "null ctx");
+    if (int rc = render_check_args("faqcs_render_device", b, d_text, d_def_pos, d_def_len, out)) return rc;
+    const uint32_t n = b->n_reads;
+    HIPCHK(hipSetDevice(c->device));
+    const size_t need = (faqcs_render_scratch_bytes(n) + sizeof(uint4) - 1) / sizeof(uint4);
+    if (need > c->s_render.cap) HIPCHK(hipStreamSynchronize(c->compute)); // (growing frees the scratch an earlier rendering may still read)
+    HIPCHK(c->s_render.reserve(need));
+    for (auto &e : c->render_ev) if (!e) HIPCHK(hipEventCreate(&e));
+    HIPCHK(hipEventRecord(c->render_ev[0], c->compute));
+    HIPCHK(faqcs_launch_render_scan(b, d_results, d_def_pos, d_def_len, d_select, d_order, out, c->s_render.p, c->compute));
+    HIPCHK(hipEventRecord(c->render_ev[1], c->compute));
+    HIPCHK(faqcs_launch_render_gather(b, d_results != nullptr, d_text, out, c->s_render.p, c->prm.input_quality_offset, c->prm.output_quality_offset,
+                                      c->prm.replace_to_N_q, c->n_cu, c->compute));
+    HIPCHK(hipEventRecord(c->render_ev[2], c->compute));
+    c->render_timed = true;
+    return 0;
+}
+
+extern "C" int faqcs_render_time_ms(faqcs_ctx *c, double *scan_ms, double *gather_ms)
+{
+    if (!c || !scan_ms || !gather_ms) return fail(FAQCS_E_INVAL, "null argument");
+    if (!c->render_timed) return fail(FAQCS_E_INVAL, "faqcs_render_time_ms: no rendering on this context yet");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipEventSynchronize(c->render_ev[2]));
+    float a = 0.f, g = 0.f;
+    HIPCHK(hipEventElapsedTime(&a, c->render_ev[0], c->render_ev[1]));
+    HIPCHK(hipEventElapsedTime(&g, c->render_ev[1], c->render_ev[2]));
+    *scan_ms = a; *gather_ms = g;
+    return 0;
+}
+
+// The host statement of the render rules (include/faqcs_mi.h at faqcs_render_device).  Two passes over the candidates: what the records need,
+// then -- when it fits -- the records.
+extern "C" int faqcs_render_host(const faqcs_params *p, const faqcs_batch *b, const faqcs_read_result *results, const uint8_t *text,
+                                 const uint32_t *def_pos, const uint32_t *def_len, const uint8_t *select, const uint32_t *order,
+                                 const faqcs_render_out *out)
+{
+    if (int rc = render_check_args("faqcs_render_host", b, text, def_pos, def_len, out)) return rc;
+    if (results && !p) return fail(FAQCS_E_INVAL, "faqcs_render_host: results without parameters");
+    const uint32_t n = b->n_reads;
+    faqcs_render_info info{};
+    for (int pass = 0; pass < 2; ++pass) {
+        uint64_t o = 0;
+        uint32_t k = 0;
+        if (pass && out->rec_offset) out->rec_offset[0] = 0;
+        for (uint32_t j = 0; j < n; ++j) {
+            const uint32_t i = order ? order[j] : j;
+            if (i >= n) continue;
+            if (select && !select[i]) continue;
+            if (results && !(results[i].flags & FAQCS_F_VALID)) continue;
+            const uint32_t a = b->offset[i], L = b->offset[i + 1] - a;
+            const uint32_t start = results ? results[i].start : 0u, len = results ? results[i].len : L;
+            if (start + len > L) return fail(FAQCS_E_INVAL, "faqcs_render_host: window outside the read");
+            const uint64_t size = (uint64_t)def_len[i] + 2ull * len + 5ull;
+            if (pass) {
+                uint8_t *w = out->text + o;
+                memcpy(w, text + def_pos[i], def_len[i]);
+                w += def_len[i];
+                *w++ = '\n';
+                uint8_t *ws = w, *wq = w + len + 3;
+                if (results) {
+                    if (int rc = faqcs_apply_edits(p, b->seq + a, b->qual + a, L, results + i, ws, wq)) return rc;
+                } else {
+                    memcpy(ws, b->seq + a, len);
+                    memcpy(wq, b->qual + a, len);
+                }
+                ws[len] = '\n'; ws[len + 1] = '+'; ws[len + 2] = '\n';
+                wq[len] = '\n';
+                if (out->rec_offset) out->rec_offset[k + 1] = (uint32_t)(o + size);
+                if (out->rec_index) out->rec_index[k] = i;
+            }
+            o += size; ++k;
+        }
+        if (pass) break;
+        info.n_bytes = o;
+        info.n_reads = k;
+        info.overflow = (o > out->capacity_bytes || o >= (1ull << 32)) ? 1u : 0u;
         *out->info = info;
         if (info.overflow) break;
     }

@@ -17,53 +17,19 @@
 //           addressed so that the bytes land in place (source - position inside the piece) and are merged under a byte mask.
 //           EDIT = false (--replace_to_N_q 0, input offset == output offset: the default) copies; only flagged reads touch their quality.
 // The kernels use no atomics and only vector stores.
-#include "faqcs_dev.h"
+#include "faqcs_edit_common.h"
 
 namespace {
+
+using namespace faqcs_edit; // the block scan, the terminal-'N' scan, the byte masks and the byte edits: shared with faqcs_render_kernel.hip
 
 constexpr uint32_t TILE_THREADS = 256, TILE_RPT = 4, TILE_READS = TILE_THREADS * TILE_RPT;
 constexpr uint32_t SCAN_THREADS = 1024;
 constexpr uint32_t SPAN_ITERS = 8, WAVE_BYTES = FAQCS_WAVE * 16, SPAN_BYTES = SPAN_ITERS * WAVE_BYTES;
 constexpr uint32_t GATHER_THREADS = 256;
 
-struct __attribute__((packed, aligned(1))) U128u { uint32_t w[4]; };
-
 struct TileSum { uint32_t bytes, reads; };                       // of one tile (<= 1 024 x 32 767 bytes)
 struct TilePrefix { unsigned long long bytes; uint32_t reads, pad; }; // of the tiles in front of one
-
-template <class T> __device__ __forceinline__ T wave_incl_scan(T v)
-{
-    const int lane = (int)(threadIdx.x & 63u);
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const T u = __shfl_up(v, d);
-        if (lane >= d) v += u;
-    }
-    return v;
-}
-
-// exclusive prefix of (a, b) over the threads of a block of NT threads, and the block's totals; s_a / s_b: NT / 64 entries each
-template <class TA, int NT> __device__ __forceinline__ void block_excl_scan2(TA a, uint32_t b, TA *s_a, uint32_t *s_b, TA &pre_a, uint32_t &pre_b, TA &tot_a, uint32_t &tot_b)
-{
-    constexpr int NW = NT / 64;
-    const int lane = (int)(threadIdx.x & 63u), w = (int)(threadIdx.x >> 6);
-    const TA ia = wave_incl_scan(a);
-    const uint32_t ib = wave_incl_scan(b);
-    __syncthreads(); // (the arrays may still be read from the previous call)
-    if (lane == 63) { s_a[w] = ia; s_b[w] = ib; }
-    __syncthreads();
-    TA wa = 0, ta = 0;
-    uint32_t wb = 0, tb = 0;
-#pragma unroll
-    for (int k = 0; k < NW; ++k) {
-        const TA xa = s_a[k];
-        const uint32_t xb = s_b[k];
-        if (k < w) { wa += xa; wb += xb; }
-        ta += xa; tb += xb;
-    }
-    pre_a = wa + ia - a; pre_b = wb + ib - b;
-    tot_a = ta; tot_b = tb;
-}
 
 // the four reads of a thread: kept bytes of each (0 when the read is not emitted) and the selection bits
 __device__ __forceinline__ uint32_t load_selection(const faqcs_read_result *__restrict__ res, const uint8_t *__restrict__ keep, uint32_t n, unsigned long long i0,
@@ -124,31 +90,6 @@ __global__ __launch_bounds__(SCAN_THREADS) void emit_scan_tiles(const TileSum *_
     }
 }
 
-// [lead, trail) of a read [a, b) whose first (bit 0) / last (bit 1) base is 'N': the positions that keep their quality.  Whole wave, uniform arguments.
-__device__ __forceinline__ void wave_terminal_extents(const uint8_t *__restrict__ seq, uint32_t a, uint32_t b, uint32_t bits, uint32_t &lead, uint32_t &trail)
-{
-    const uint32_t lane = threadIdx.x & 63u, L = b - a;
-    lead = 0; trail = L;
-    if (bits & 1u) {
-        lead = L;
-        for (uint32_t p = 0; p < L; p += 64) {
-            const uint32_t x = p + lane;
-            const bool stop = x >= L || seq[(size_t)a + x] != 'N';
-            const unsigned long long m = __ballot(stop);
-            if (m) { lead = p + (uint32_t)__builtin_ctzll(m); break; }
-        }
-    }
-    if (bits & 2u) {
-        trail = 0;
-        for (uint32_t p = 0; p < L; p += 64) { // x: distance from the read's last base
-            const uint32_t x = p + lane;
-            const bool stop = x >= L || seq[(size_t)b - 1 - x] != 'N';
-            const unsigned long long m = __ballot(stop);
-            if (m) { trail = L - (p + (uint32_t)__builtin_ctzll(m)); break; }
-        }
-    }
-}
-
 __global__ __launch_bounds__(TILE_THREADS) void emit_scan_apply(const uint8_t *__restrict__ seq, const uint32_t *__restrict__ in_off, const uint8_t *__restrict__ tn,
                                                                 const faqcs_read_result *__restrict__ res, const uint8_t *__restrict__ keep, const uint32_t n,
                                                                 const TilePrefix *__restrict__ prefix, const faqcs_emit_info *__restrict__ info,
@@ -202,36 +143,6 @@ __global__ __launch_bounds__(TILE_THREADS) void emit_scan_apply(const uint8_t *_
             }
         }
     }
-}
-
-// bytes [lo, hi) of a 16-byte piece that lie in its dword j, as a mask of 0xff bytes
-__device__ __forceinline__ uint32_t byte_range_mask(int lo, int hi, int j)
-{
-    int a = lo - 4 * j, b = hi - 4 * j;
-    a = a < 0 ? 0 : (a > 4 ? 4 : a);
-    b = b < 0 ? 0 : (b > 4 ? 4 : b);
-    if (b <= a) return 0u;
-    const uint32_t mb = b == 4 ? 0xffffffffu : ((1u << (8 * b)) - 1u);
-    const uint32_t ma = (1u << (8 * a)) - 1u; // a < 4 here
-    return mb & ~ma;
-}
-
-// faqcs_apply_edits() on the four bytes of a dword pair (quality already masked)
-__device__ __forceinline__ void edit_dword(uint32_t &s, uint32_t &q, int in, int out, int replace_q)
-{
-    uint32_t so = 0, qo = 0;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        uint32_t b = (s >> (8 * t)) & 0xffu;
-        const int raw = (int)(int8_t)((q >> (8 * t)) & 0xffu);
-        int qs = raw - in;
-        qs = qs < 0 ? 0 : qs;
-        if (replace_q > 0 && b == 'G' && qs < replace_q) b = 'N';
-        const uint32_t qb = in != out ? (uint32_t)(qs + out) & 0xffu : (uint32_t)raw & 0xffu;
-        so |= b << (8 * t);
-        qo |= qb << (8 * t);
-    }
-    s = so; q = qo;
 }
 
 template <bool EDIT>
@@ -306,10 +217,8 @@ __global__ __launch_bounds__(GATHER_THREADS) void emit_gather(const uint8_t *__r
                         for (int j = 0; j < 4; ++j) {
                             const uint32_t m = (d == 0 && e == 16) ? 0xffffffffu : byte_range_mask(d, e, j);
                             uint32_t s = vs.w[j], q = vq.w[j];
-                            if (flagged) {
-                                const uint32_t km = byte_range_mask(keep_lo < d ? d : keep_lo, keep_hi > e ? e : keep_hi, j);
-                                q = (q & km) | (in4 & ~km);
-                            }
+                            if (flagged)
+                                q = mask_terminal_quality(q, keep_lo < d ? d : keep_lo, keep_hi > e ? e : keep_hi, j, in4);
                             if (EDIT) edit_dword(s, q, in, out, replace_q);
                             as[j] = (as[j] & ~m) | (s & m);
                             aq[j] = (aq[j] & ~m) | (q & m);

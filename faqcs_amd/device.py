@@ -1,5 +1,5 @@
 """Torch-facing helpers of the device seam: inputs and outputs are torch tensors that live on the GPU; the work is the
-library's HIP kernels (faqcs_emit_device), never torch ops."""
+library's HIP kernels (faqcs_emit_device, faqcs_render_device), never torch ops."""
 import ctypes as C
 
 from . import _capi as capi
@@ -42,3 +42,40 @@ def trimmed_reads(engine, seq, qual, offset, results, keep=None, terminal_n=None
         raise FaqcsError(capi.E_INVAL, "faqcs_emit_device: the emission needs %d bytes, the output arenas hold %d" % (n_bytes, cap))
     a, b = front + shift[0], front + shift[1]
     return o_seq[a:a + n_bytes], o_qual[b:b + n_bytes], o_off[:n_emit + 1], o_idx[:n_emit]
+
+
+def rendered_fastq(engine, text, def_pos, def_len, seq, qual, offset, results=None, select=None, order=None, terminal_n=None, capacity=None):
+    """The FASTQ text of one output file of a device-resident batch, assembled on the device (faqcs_render_device).
+
+    text: uint8 CUDA tensor whose element 0 is byte 0 of the FASTQ text faqcs_parse_device() indexed (its padding: 16 readable bytes in
+    front, 64 behind -- pass a view into a larger tensor); def_pos / def_len: int32 / uint32 tensors [n], the defline spans that parse
+    delivered; seq / qual / offset / terminal_n: the batch, as for trimmed_reads(); results: the (n, 4) int16 tensor faqcs_submit_device()
+    filled on `engine` -- the trimmed, edited records -- or None for the original records (the discard stream); select: optional uint8 /
+    bool tensor [n] (0 = do not render); order: optional int32 tensor [n], candidate j is read order[j].  capacity: bytes of text to make
+    room for (default: the input text's size plus 5 bytes per read, which no rendering of distinct reads exceeds).
+    Returns (text, rec_offset): uint8 [n_bytes] -- a view that starts 16-byte aligned --, int32 [n_rendered + 1] (bit pattern of uint32)."""
+    import torch
+
+    n = int(offset.numel()) - 1
+    dev = seq.device
+    cap = int(text.numel()) + 5 * n if capacity is None else int(capacity)
+    o_text = torch.empty(cap + capi.ARENA_PAD_AFTER + 16, dtype=torch.uint8, device=dev)
+    o_off = torch.empty(n + 1, dtype=torch.int32, device=dev)
+    info = torch.zeros(2, dtype=torch.int64, device=dev)
+    shift = (-o_text.data_ptr()) % 16
+    if select is not None:
+        select = select.to(torch.uint8).contiguous()
+    if order is not None:
+        order = order.to(torch.int32).contiguous()
+    batch = capi.Batch(seq.data_ptr(), qual.data_ptr(), offset.data_ptr(), n, 0, None, 0,
+                       terminal_n.data_ptr() if terminal_n is not None and n else None)
+    out = capi.RenderOut(o_text.data_ptr() + shift, cap, o_off.data_ptr(), None, info.data_ptr())
+    torch.cuda.current_stream(dev).synchronize()  # the library's compute stream is its own: the inputs must be complete
+    engine.render_device(batch, results.data_ptr() if results is not None else None, text.data_ptr(), def_pos.data_ptr(), def_len.data_ptr(), out,
+                         select.data_ptr() if select is not None and n else None, order.data_ptr() if order is not None and n else None)
+    engine.sync()
+    h = info.cpu().numpy()
+    n_bytes, n_rec, overflow = int(h[0]), int(h[1]) & 0xFFFFFFFF, int(h[1]) >> 32
+    if overflow:
+        raise FaqcsError(capi.E_INVAL, "faqcs_render_device: the text needs %d bytes, the output holds %d" % (n_bytes, cap))
+    return o_text[shift:shift + n_bytes], o_off[:n_rec + 1]

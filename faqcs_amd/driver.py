@@ -217,6 +217,41 @@ def emit_model(opt, in_off, seq, qual, offset, res, keep=None):
     return es[src], eq[src], out_off.astype(np.uint32), index
 
 
+def render_model(opt, in_off, text, def_pos, def_len, seq, qual, offset, res=None, select=None, order=None):
+    """What faqcs_render_device() / faqcs_render_host() write, as numpy, from the rules of include/faqcs_mi.h: candidate j is read order[j]
+    (j without an order; an entry >= n is skipped); it is rendered when select[i] != 0 (or no select) and, with results, F_VALID; the record
+    is defline \\n S \\n+\\n Q \\n with S / Q the kept window cut out of edited_arenas() (results given: Run.write_read) or the read as it came
+    (res None: the discard stream, _write_raw).  -> (text uint8, rec_offset uint32[n_rendered + 1], rec_index uint32[n_rendered])"""
+    offset = np.asarray(offset)
+    n = len(offset) - 1
+    cand = np.arange(n, dtype=np.int64) if order is None else np.asarray(order).astype(np.int64)[:n]
+    cand = cand[(cand >= 0) & (cand < n)]
+    ok = np.ones(len(cand), dtype=bool)
+    if select is not None:
+        ok &= np.asarray(select)[cand] != 0
+    if res is not None:
+        ok &= (res["flags"][cand] & capi.F_VALID) != 0
+    index = cand[ok]
+    if res is not None:
+        es, eq = edited_arenas(opt, in_off, seq, qual, offset)
+        first = offset[index].astype(np.int64) + res["start"][index].astype(np.int64)
+        lens = res["len"][index].astype(np.int64)
+    else:
+        es, eq = np.asarray(seq), np.asarray(qual)
+        first = offset[index].astype(np.int64)
+        lens = offset[index + 1].astype(np.int64) - first
+    text = np.asarray(text)
+    pieces = []
+    for k, i in enumerate(index):
+        a, b, d = int(first[k]), int(first[k] + lens[k]), int(def_pos[i])
+        pieces += [text[d:d + int(def_len[i])].tobytes(), b"\n", es[a:b].tobytes(), b"\n+\n", eq[a:b].tobytes(), b"\n"]
+    rec_offset = np.zeros(len(index) + 1, dtype=np.int64)
+    rec_offset[1:] = np.cumsum(np.asarray(def_len)[index].astype(np.int64) + 2 * lens + 5)
+    out = np.frombuffer(b"".join(pieces), dtype=np.uint8)
+    assert len(out) == int(rec_offset[-1])
+    return out, rec_offset.astype(np.uint32), index.astype(np.uint32)
+
+
 class Run:
     """State the reference keeps in main(): filter_stats, adapter_stats, PlotInfo, Options (FaQCs.cpp:67-69)."""
 

@@ -79,6 +79,19 @@ class HipEngine:
         _check(self.lib, self.lib.faqcs_parse_time_ms(self.ctx, C.byref(a), C.byref(g)))
         return a.value, g.value
 
+    def render_device(self, batch, d_results, d_text, d_def_pos, d_def_len, out, d_select=None, d_order=None):
+        """faqcs_render_device: the FASTQ text of the selected reads of a device-resident batch (a capi.Batch of device pointers, as given to
+        faqcs_submit_device) into the arrays of `out` (a capi.RenderOut of device pointers).  d_results: the device results (the trimmed
+        records) or None (the original records: the discard stream); d_text / d_def_pos / d_def_len: the text and the defline spans
+        faqcs_parse_device delivered; d_select / d_order: optional device arrays (include/faqcs_mi.h).  Enqueued; sync() waits."""
+        _check(self.lib, self.lib.faqcs_render_device(self.ctx, C.byref(batch), d_results, d_text, d_def_pos, d_def_len, d_select, d_order, C.byref(out)))
+
+    def render_time_ms(self):
+        """(scan ms, gather ms) of the last render_device() on this engine (HIP events on the compute stream); waits for it."""
+        a, g = C.c_double(), C.c_double()
+        _check(self.lib, self.lib.faqcs_render_time_ms(self.ctx, C.byref(a), C.byref(g)))
+        return a.value, g.value
+
     def set_quality(self, q):
         _check(self.lib, self.lib.faqcs_set_quality(self.ctx, int(q)))
 

@@ -33,7 +33,8 @@ extern "C" {
  * only moves them) -- a run of up to 17 consecutive k-mers each instead of one (key, epoch) pair -- and nothing about their size or the calls.
  * Round 6 adds faqcs_kmer_finish_pass, and faqcs_sync() no longer counts the k-mers that wait in the open group (see below).
  * faqcs_emit_device (the trimmed, edited reads packed on the device) is a new entry point with structures of its own, and so are
- * faqcs_parse_device / faqcs_parse_host (FASTQ text to a packed batch). */
+ * faqcs_parse_device / faqcs_parse_host (FASTQ text to a packed batch) and faqcs_render_device / faqcs_render_host (the FASTQ text of the
+ * output files). */
 #define FAQCS_ABI_VERSION 2
 
 /* FilterStat enum order, FaQCs.h:46-75 */
@@ -307,6 +308,51 @@ typedef struct faqcs_parse_out {
 int  faqcs_parse_device(faqcs_ctx *ctx, const uint8_t *d_text, uint64_t n_text, int final, const faqcs_parse_out *out);
 int  faqcs_parse_host(const uint8_t *text, uint64_t n_text, int final, const faqcs_parse_out *out);
 
+/* The last step of the device seam: the records the reference writes to its files (FaQCs.cpp:296-361), as FASTQ text in device memory.
+ * Bases and qualities are read straight from the batch's arenas, the deflines from the text faqcs_parse_device() indexed.
+ * The rules:
+ *   - which reads are rendered.  d_order (OPTIONAL) has n_reads entries: candidate j is read d_order[j]; an entry >= n_reads is skipped
+ *     and never dereferenced; NULL means input order (candidate j is read j).  A candidate i is rendered when (d_select == NULL or
+ *     d_select[i] != 0) and, when d_results != NULL, d_results[i].flags & FAQCS_F_VALID.  Rendered records keep candidate order.
+ *   - d_results != NULL (the trimmed streams): the record is  defline '\n' S "\n+\n" Q '\n'  where S / Q are exactly what
+ *     faqcs_apply_edits() writes for that read's window, with the context's input_quality_offset, output_quality_offset and replace_to_N_q
+ *     (and batch->terminal_n when present): def_len + 2 len + 5 bytes, the bytes of Run::write_read.
+ *   - d_results == NULL (the discard stream): the ORIGINAL record -- the whole read, no edit, no re-basing -- in the same form: the bytes
+ *     of Run::write_raw.
+ *   - the defline of read i is d_text[d_def_pos[i] .. + d_def_len[i]), exactly as faqcs_parse_device() delivered it.  It is not checked
+ *     and may be empty.
+ *   - out->info is ALWAYS complete: the bytes and the records the rendering needs.  n_bytes > capacity_bytes or n_bytes >= 2^32 (text
+ *     positions are 32 bits wide) sets overflow = 1 and NOTHING but info is written: no truncation, ever.  Otherwise only
+ *     text[0 .. n_bytes rounded up to 16) (whole 16-byte pieces are stored), rec_offset[0 .. n_reads] and rec_index[0 .. n_reads) are
+ *     touched, with n_reads = info->n_reads.  A batch without reads, or of which nothing is rendered, yields zeros (and rec_offset[0] = 0).
+ * faqcs_render_device: every pointer but ctx, batch and out is a DEVICE pointer, and so are batch->seq / qual / offset / terminal_n and every
+ * pointer of *out (out->info included); batch->segment_start is not needed.  batch and d_results are what faqcs_submit_device() took and
+ * filled; d_text needs the padding faqcs_parse_device() asks for (FAQCS_ARENA_PAD_BEFORE readable bytes in front of it, FAQCS_ARENA_PAD_AFTER
+ * behind the last defline), the arenas that of faqcs_batch.  The call is enqueued on the context's compute stream behind the submission and
+ * returns at once: the host never waits for a count; faqcs_sync() waits.  With both mates of a paired run in one batch -- read i of mate 2
+ * at m + i -- the four files are four calls: QC.1 select [v1 & v2, 0], QC.2 select [0, v1 & v2], unpaired select
+ * [v1 ^ v2, v1 ^ v2] in the order [0, m, 1, m + 1, ...], discard without results, select [!v1, !v2] in the same order.
+ * Scratch (36 bytes per read) is the library's: grown on demand, freed by faqcs_destroy().
+ * FAQCS_E_INVAL: a null ctx / batch / d_text (with reads) / batch arrays (with reads) / d_def_pos / d_def_len / out / out->text / out->info,
+ * or out->text not 16-byte aligned.
+ * faqcs_render_host is the same with HOST pointers: the host statement of these rules, plain single-threaded C++ with no HIP call (no
+ * padding is needed anywhere, exactly [0, n_bytes) of the text is written, batch->terminal_n is not looked at; p may be NULL without
+ * results; a window that leaves its read is FAQCS_E_INVAL). */
+typedef struct faqcs_render_info { uint64_t n_bytes; uint32_t n_reads; uint32_t overflow; } faqcs_render_info;
+typedef struct faqcs_render_out {
+    uint8_t  *text;            /* 16-byte aligned; capacity_bytes + FAQCS_ARENA_PAD_AFTER writable */
+    uint64_t  capacity_bytes;
+    uint32_t *rec_offset;      /* OPTIONAL, batch->n_reads + 1: [0] = 0, [k + 1] = end of rendered record k */
+    uint32_t *rec_index;       /* OPTIONAL, batch->n_reads: input read of rendered record k */
+    faqcs_render_info *info;
+} faqcs_render_out;
+int  faqcs_render_device(faqcs_ctx *ctx, const faqcs_batch *batch, const faqcs_read_result *d_results,
+                         const uint8_t *d_text, const uint32_t *d_def_pos, const uint32_t *d_def_len,
+                         const uint8_t *d_select, const uint32_t *d_order, const faqcs_render_out *out);
+int  faqcs_render_host(const faqcs_params *p, const faqcs_batch *batch, const faqcs_read_result *results,
+                       const uint8_t *text, const uint32_t *def_pos, const uint32_t *def_len,
+                       const uint8_t *select, const uint32_t *order, const faqcs_render_out *out);
+
 /* Pipelined form of faqcs_submit(): returns a ticket; faqcs_wait(ticket) blocks until THAT batch's results have
  * landed in `results` (later batches may still be in flight: two input staging slots let the H2D copy of batch
  * k+1 overlap the kernels of batch k).  Host arenas / result arrays obtained from faqcs_host_alloc() are pinned,
@@ -437,6 +483,8 @@ int  faqcs_synth_fill_genome(int device_id, uint8_t *d_seq, uint8_t *d_qual, uin
 int  faqcs_emit_time_ms(faqcs_ctx *ctx, double *scan_ms, double *gather_ms);
 /* the same for the LAST faqcs_parse_device() on the context: the line index and the records (index_ms), the gather (gather_ms) */
 int  faqcs_parse_time_ms(faqcs_ctx *ctx, double *index_ms, double *gather_ms);
+/* the same for the LAST faqcs_render_device() on the context: the scan (scan_ms), the gather (gather_ms) */
+int  faqcs_render_time_ms(faqcs_ctx *ctx, double *scan_ms, double *gather_ms);
 /* diagnostic builds only: section clocks accumulated by the trim kernel (16 words; read and cleared) */
 int  faqcs_debug_words(faqcs_ctx *ctx, uint64_t *out, uint32_t n);
 /* average duration (ms) of the dominant kernel over the launches since the last call, measured with
