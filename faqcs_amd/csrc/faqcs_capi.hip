@@ -72,6 +72,8 @@ static int fail(int code, const std::string &msg) { g_err = msg; return code; }
             return fail(FAQCS_E_NODEVICE, std::string(#x) + ": " + hipGetErrorString(e_));                \
     } while (0)
 
+struct faqcs_ctx;
+
 namespace {
 
 template <class T> struct DevBuf {
@@ -93,6 +95,19 @@ template <class T> struct DevBuf {
 // p .. a: the adapter pre-pass (when there is one), a .. b: the trim kernel, k0 .. k1: the submission's k-mer kernels (kmer_count, or
 // kmer_extract in the owner-partitioned mode)
 struct Timing { hipEvent_t a, b, p, k0, k1; bool adapter, kmer; };
+
+// What faqcs_emit_device / faqcs_parse_device / faqcs_render_device each keep on a context: the scratch of their kernels and the events
+// around the two stages of the last call (faqcs_*_time_ms).  A stage is whatever is launched between two marks.
+struct PackStage {
+    DevBuf<uint4> scratch;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    hipStream_t st = nullptr;
+    bool timed = false;
+    int begin(faqcs_ctx *c, size_t scratch_bytes); // the scratch, and the mark in front of the first stage
+    int mark(int i);                               // behind stage i (1, 2)
+    int times(faqcs_ctx *c, const char *not_yet, double *first_ms, double *second_ms);
+    void release();
+};
 
 } // namespace
 
@@ -131,15 +146,9 @@ struct faqcs_ctx {
     DevBuf<uint32_t> s_seg, s_sl;
     DevBuf<uint16_t> s_hit;
     DevBuf<faqcs_read_result> s_res;
-    DevBuf<uint4> s_emit; // faqcs_emit_device: the scan's tile sums and the 16-byte record of every emitted read
-    hipEvent_t emit_ev[3] = {nullptr, nullptr, nullptr}; // around the scan and the gather of the last emission (faqcs_emit_time_ms)
-    bool emit_timed = false;
-    DevBuf<uint4> s_parse; // faqcs_parse_device: the line index, the record lengths and the two scans' tile sums
-    hipEvent_t parse_ev[3] = {nullptr, nullptr, nullptr}; // around the index + records and the gather of the last parse (faqcs_parse_time_ms)
-    bool parse_timed = false;
-    DevBuf<uint4> s_render; // faqcs_render_device: the 32-byte descriptor and the text offset of every rendered record, the scan's tile sums
-    hipEvent_t render_ev[3] = {nullptr, nullptr, nullptr}; // around the scan and the gather of the last rendering (faqcs_render_time_ms)
-    bool render_timed = false;
+    PackStage emit;   // the scan's tile sums and the 16-byte record of every emitted read | scan, gather
+    PackStage parse;  // the line index, the record lengths and the two scans' tile sums | index + records, gather
+    PackStage render; // the 32-byte descriptor and the text offset of every rendered record, the scan's tile sums | scan, gather
     // per-read composition records (trim kernel -> composition_histogram).  Two sets: the histogram kernels of
     // submission k run on the aux stream next to the trim kernel of submission k+1 (LDS-bound next to VALU-bound).
     struct RecSet { DevBuf<unsigned long long> pre, post; hipEvent_t trimmed = nullptr, folded = nullptr; bool used = false; };
@@ -524,9 +533,7 @@ extern "C" void faqcs_destroy(faqcs_ctx *c)
     for (auto &t : c->timings) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); (void)hipEventDestroy(t.p); (void)hipEventDestroy(t.k0); (void)hipEventDestroy(t.k1); }
     if (c->comm) comm_release(c->comm);
     if (c->comm_ev) (void)hipEventDestroy(c->comm_ev);
-    for (auto &e : c->emit_ev) if (e) (void)hipEventDestroy(e);
-    for (auto &e : c->render_ev) if (e) (void)hipEventDestroy(e);
-    for (auto &e : c->parse_ev) if (e) (void)hipEventDestroy(e);
+    c->emit.release(); c->parse.release(); c->render.release();
     if (c->ins_a) (void)hipEventDestroy(c->ins_a);
     if (c->ins_b) (void)hipEventDestroy(c->ins_b);
     for (int k = 0; k < 2; ++k) { if (c->fwd_free[k]) (void)hipEventDestroy(c->fwd_free[k]); if (c->fwd_copied[k]) (void)hipEventDestroy(c->fwd_copied[k]); c->fwd_items[k].release(); }
@@ -535,7 +542,7 @@ extern "C" void faqcs_destroy(faqcs_ctx *c)
     for (void *q : ptrs) if (q) (void)hipFree(q);
     for (auto &sl : c->slot) { sl.seq.release(); sl.qual.release(); sl.tn.release(); sl.off.release(); if (sl.done) (void)hipEventDestroy(sl.done); }
     for (auto &e : c->ticket_ev) if (e) (void)hipEventDestroy(e);
-    c->s_seg.release(); c->s_sl.release(); c->s_hit.release(); c->s_res.release(); c->s_emit.release(); c->s_parse.release(); c->s_render.release(); c->s_astate.release(); c->s_amask.release();
+    c->s_seg.release(); c->s_sl.release(); c->s_hit.release(); c->s_res.release(); c->s_astate.release(); c->s_amask.release();
     for (auto &rs : c->rec) { rs.pre.release(); rs.post.release(); if (rs.trimmed) (void)hipEventDestroy(rs.trimmed); if (rs.folded) (void)hipEventDestroy(rs.folded); }
     if (c->aux) (void)hipStreamDestroy(c->aux);
     c->ob_items.release(); c->ob_wave_count.release(); c->ob_wave_offset.release();
@@ -1283,6 +1290,41 @@ extern "C" int faqcs_submit_device(faqcs_ctx *c, const faqcs_batch *b, faqcs_rea
     return enqueue(c, b->seq, b->qual, b->offset, n, max_len, b->segment_start, b->n_segments, d_results, b->terminal_n);
 }
 
+int PackStage::begin(faqcs_ctx *c, size_t scratch_bytes)
+{
+    HIPCHK(hipSetDevice(c->device));
+    st = c->compute;
+    const size_t need = (scratch_bytes + sizeof(uint4) - 1) / sizeof(uint4);
+    if (need > scratch.cap) HIPCHK(hipStreamSynchronize(st)); // (growing frees the scratch an earlier call may still read)
+    HIPCHK(scratch.reserve(need));
+    for (auto &e : ev) if (!e) HIPCHK(hipEventCreate(&e));
+    return mark(0);
+}
+
+int PackStage::mark(int i)
+{
+    HIPCHK(hipEventRecord(ev[i], st));
+    if (i == 2) timed = true;
+    return 0;
+}
+
+int PackStage::times(faqcs_ctx *c, const char *not_yet, double *first_ms, double *second_ms)
+{
+    if (!timed) return fail(FAQCS_E_INVAL, not_yet);
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipEventSynchronize(ev[2]));
+    float ms[2] = {0.f, 0.f};
+    for (int i = 0; i < 2; ++i) HIPCHK(hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]));
+    *first_ms = ms[0]; *second_ms = ms[1];
+    return 0;
+}
+
+void PackStage::release()
+{
+    scratch.release();
+    for (auto &e : ev) if (e) (void)hipEventDestroy(e);
+}
+
 extern "C" int faqcs_emit_device(faqcs_ctx *c, const faqcs_batch *b, const faqcs_read_result *d_results, const uint8_t *d_keep, const faqcs_emit_out *out)
 {
     if (!c) return fail(FAQCS_E_INVAL, "null ctx");
@@ -1291,32 +1333,18 @@ extern "C" int faqcs_emit_device(faqcs_ctx *c, const faqcs_batch *b, const faqcs
     if (((uintptr_t)out->seq | (uintptr_t)out->qual) & 15u) return fail(FAQCS_E_INVAL, "faqcs_emit_device: the output arenas must be 16-byte aligned");
     const uint32_t n = b->n_reads;
     if (n && (!b->seq || !b->qual || !b->offset)) return fail(FAQCS_E_INVAL, "faqcs_emit_device: null batch arrays");
-    HIPCHK(hipSetDevice(c->device));
-    const size_t need = (faqcs_emit_scratch_bytes(n) + sizeof(uint4) - 1) / sizeof(uint4);
-    if (need > c->s_emit.cap) HIPCHK(hipStreamSynchronize(c->compute)); // (growing frees the scratch an earlier emission may still read)
-    HIPCHK(c->s_emit.reserve(need));
-    for (auto &e : c->emit_ev) if (!e) HIPCHK(hipEventCreate(&e));
-    HIPCHK(hipEventRecord(c->emit_ev[0], c->compute));
-    HIPCHK(faqcs_launch_emit_scan(b->seq, b->offset, b->terminal_n, n, d_results, d_keep, out, c->s_emit.p, c->compute));
-    HIPCHK(hipEventRecord(c->emit_ev[1], c->compute));
-    HIPCHK(faqcs_launch_emit_gather(b->seq, b->qual, n, out, c->s_emit.p, c->prm.input_quality_offset, c->prm.output_quality_offset,
+    if (int rc = c->emit.begin(c, faqcs_emit_scratch_bytes(n))) return rc;
+    HIPCHK(faqcs_launch_emit_scan(b->seq, b->offset, b->terminal_n, n, d_results, d_keep, out, c->emit.scratch.p, c->compute));
+    if (int rc = c->emit.mark(1)) return rc;
+    HIPCHK(faqcs_launch_emit_gather(b->seq, b->qual, n, out, c->emit.scratch.p, c->prm.input_quality_offset, c->prm.output_quality_offset,
                                     c->prm.replace_to_N_q, c->n_cu, c->compute));
-    HIPCHK(hipEventRecord(c->emit_ev[2], c->compute));
-    c->emit_timed = true;
-    return 0;
+    return c->emit.mark(2);
 }
 
 extern "C" int faqcs_emit_time_ms(faqcs_ctx *c, double *scan_ms, double *gather_ms)
 {
     if (!c || !scan_ms || !gather_ms) return fail(FAQCS_E_INVAL, "null argument");
-    if (!c->emit_timed) return fail(FAQCS_E_INVAL, "faqcs_emit_time_ms: no emission on this context yet");
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipEventSynchronize(c->emit_ev[2]));
-    float a = 0.f, g = 0.f;
-    HIPCHK(hipEventElapsedTime(&a, c->emit_ev[0], c->emit_ev[1]));
-    HIPCHK(hipEventElapsedTime(&g, c->emit_ev[1], c->emit_ev[2]));
-    *scan_ms = a; *gather_ms = g;
-    return 0;
+    return c->emit.times(c, "faqcs_emit_time_ms: no emission on this context yet", scan_ms, gather_ms);
 }
 
 static const char *const PARSE_TEXT[] = {"", "fastq.cpp:next_read: Unable to read sequence", "fastq.cpp:next_read: Unable to read '+'",
@@ -1339,32 +1367,18 @@ extern "C" int faqcs_parse_device(faqcs_ctx *c, const uint8_t *d_text, uint64_t 
 {
     if (!c) return fail(FAQCS_E_INVAL, "null ctx");
     if (int rc = parse_check_args("faqcs_parse_device", d_text, n_text, out)) return rc;
-    HIPCHK(hipSetDevice(c->device));
-    const size_t need = (faqcs_parse_scratch_bytes(n_text) + sizeof(uint4) - 1) / sizeof(uint4);
-    if (need > c->s_parse.cap) HIPCHK(hipStreamSynchronize(c->compute)); // (growing frees the scratch an earlier parse may still read)
-    HIPCHK(c->s_parse.reserve(need));
-    for (auto &e : c->parse_ev) if (!e) HIPCHK(hipEventCreate(&e));
-    HIPCHK(hipEventRecord(c->parse_ev[0], c->compute));
-    HIPCHK(faqcs_launch_parse_index(d_text, n_text, final ? 1 : 0, c->s_parse.p, c->compute));
-    HIPCHK(faqcs_launch_parse_records(d_text, n_text, out, c->s_parse.p, c->n_cu, c->compute));
-    HIPCHK(hipEventRecord(c->parse_ev[1], c->compute));
-    HIPCHK(faqcs_launch_parse_gather(d_text, n_text, out, c->s_parse.p, c->n_cu, c->compute));
-    HIPCHK(hipEventRecord(c->parse_ev[2], c->compute));
-    c->parse_timed = true;
-    return 0;
+    if (int rc = c->parse.begin(c, faqcs_parse_scratch_bytes(n_text))) return rc;
+    HIPCHK(faqcs_launch_parse_index(d_text, n_text, final ? 1 : 0, c->parse.scratch.p, c->compute));
+    HIPCHK(faqcs_launch_parse_records(d_text, n_text, out, c->parse.scratch.p, c->n_cu, c->compute));
+    if (int rc = c->parse.mark(1)) return rc;
+    HIPCHK(faqcs_launch_parse_gather(d_text, n_text, out, c->parse.scratch.p, c->n_cu, c->compute));
+    return c->parse.mark(2);
 }
 
 extern "C" int faqcs_parse_time_ms(faqcs_ctx *c, double *index_ms, double *gather_ms)
 {
     if (!c || !index_ms || !gather_ms) return fail(FAQCS_E_INVAL, "null argument");
-    if (!c->parse_timed) return fail(FAQCS_E_INVAL, "faqcs_parse_time_ms: no parse on this context yet");
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipEventSynchronize(c->parse_ev[2]));
-    float a = 0.f, g = 0.f;
-    HIPCHK(hipEventElapsedTime(&a, c->parse_ev[0], c->parse_ev[1]));
-    HIPCHK(hipEventElapsedTime(&g, c->parse_ev[1], c->parse_ev[2]));
-    *index_ms = a; *gather_ms = g;
-    return 0;
+    return c->parse.times(c, "faqcs_parse_time_ms: no parse on this context yet", index_ms, gather_ms);
 }
 
 // The host statement of the parse rules (include/faqcs_mi.h at faqcs_parse_device).  Two passes over the text: what the records need, then --
@@ -1453,32 +1467,18 @@ extern "C" int faqcs_render_device(faqcs_ctx *c, const faqcs_batch *b, const faq
     if (!c) return fail(FAQCS_E_INVAL, "null ctx");
     if (int rc = render_check_args("faqcs_render_device", b, d_text, d_def_pos, d_def_len, out)) return rc;
     const uint32_t n = b->n_reads;
-    HIPCHK(hipSetDevice(c->device));
-    const size_t need = (faqcs_render_scratch_bytes(n) + sizeof(uint4) - 1) / sizeof(uint4);
-    if (need > c->s_render.cap) HIPCHK(hipStreamSynchronize(c->compute)); // (growing frees the scratch an earlier rendering may still read)
-    HIPCHK(c->s_render.reserve(need));
-    for (auto &e : c->render_ev) if (!e) HIPCHK(hipEventCreate(&e));
-    HIPCHK(hipEventRecord(c->render_ev[0], c->compute));
-    HIPCHK(faqcs_launch_render_scan(b, d_results, d_def_pos, d_def_len, d_select, d_order, out, c->s_render.p, c->compute));
-    HIPCHK(hipEventRecord(c->render_ev[1], c->compute));
-    HIPCHK(faqcs_launch_render_gather(b, d_results != nullptr, d_text, out, c->s_render.p, c->prm.input_quality_offset, c->prm.output_quality_offset,
+    if (int rc = c->render.begin(c, faqcs_render_scratch_bytes(n))) return rc;
+    HIPCHK(faqcs_launch_render_scan(b, d_results, d_def_pos, d_def_len, d_select, d_order, out, c->render.scratch.p, c->compute));
+    if (int rc = c->render.mark(1)) return rc;
+    HIPCHK(faqcs_launch_render_gather(b, d_results != nullptr, d_text, out, c->render.scratch.p, c->prm.input_quality_offset, c->prm.output_quality_offset,
                                       c->prm.replace_to_N_q, c->n_cu, c->compute));
-    HIPCHK(hipEventRecord(c->render_ev[2], c->compute));
-    c->render_timed = true;
-    return 0;
+    return c->render.mark(2);
 }
 
 extern "C" int faqcs_render_time_ms(faqcs_ctx *c, double *scan_ms, double *gather_ms)
 {
     if (!c || !scan_ms || !gather_ms) return fail(FAQCS_E_INVAL, "null argument");
-    if (!c->render_timed) return fail(FAQCS_E_INVAL, "faqcs_render_time_ms: no rendering on this context yet");
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipEventSynchronize(c->render_ev[2]));
-    float a = 0.f, g = 0.f;
-    HIPCHK(hipEventElapsedTime(&a, c->render_ev[0], c->render_ev[1]));
-    HIPCHK(hipEventElapsedTime(&g, c->render_ev[1], c->render_ev[2]));
-    *scan_ms = a; *gather_ms = g;
-    return 0;
+    return c->render.times(c, "faqcs_render_time_ms: no rendering on this context yet", scan_ms, gather_ms);
 }
 
 // The host statement of the render rules (include/faqcs_mi.h at faqcs_render_device).  Two passes over the candidates: what the records need,

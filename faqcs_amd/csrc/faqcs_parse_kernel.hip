@@ -14,59 +14,25 @@
 //            '\r', 16 bytes per step) and checks the length rule.  A tile is 256 records; its sums stop at its first bad record.  One block
 //            finds the first bad record of the text, scans the tile sums in 64 bits and completes faqcs_parse_info, overflow included.
 //            The last pass writes offset, terminal_n and the defline spans of the records in front of the bad one.
-//   gather   parse_gather.  OUTPUT-centric like emit_gather<false> (faqcs_emit_kernel.hip): a lane owns one aligned 16-byte piece of the
-//            two arenas, finds its record among the output offsets, loads 16 unaligned bytes from the base line and from the quality line
+//   gather   parse_gather: for_each_piece_segment (faqcs_pack_common.h) over out->offset with ParsePiece.  A lane owns one aligned 16-byte
+//            piece of the two arenas, loads 16 unaligned bytes from the base line and from the quality line of its record
 //            (text + source - position in the piece) and merges under a byte mask where a piece straddles records.
 // The kernels use no global atomics and only vector stores.
-#include "faqcs_dev.h"
+#include "faqcs_pack_common.h"
 
 namespace {
 
+using namespace faqcs_pack; // the block scan, the piece walker and the byte masks
+
 constexpr uint32_t TEXT_THREADS = 256, TEXT_PPT = 4, TEXT_PIECES = TEXT_THREADS * TEXT_PPT, TEXT_TILE = TEXT_PIECES * 16; // 16 KiB
 constexpr uint32_t REC_THREADS = 256;  // records of a tile, one per thread
-constexpr uint32_t SCAN_THREADS = 1024;
-constexpr uint32_t SPAN_ITERS = 8, WAVE_BYTES = FAQCS_WAVE * 16, SPAN_BYTES = SPAN_ITERS * WAVE_BYTES;
-constexpr uint32_t GATHER_THREADS = 256;
 constexpr uint32_t NONE = 0xffffffffu;
-
-struct __attribute__((packed, aligned(1))) U128u { uint32_t w[4]; };
 
 struct TextTile { uint32_t nl, cr; };
 // what the index found (device side; the host sizes nothing by it)
 struct Hdr { uint32_t n_nl, has_cr, n_cand, tail_err, n_rec_tiles, pad[3]; };
 // of the records of one tile IN FRONT OF its first bad record
 struct RecTile { unsigned long long bytes; uint32_t first_bad, max_len; };
-
-template <class T> __device__ __forceinline__ T wave_incl_scan(T v)
-{
-    const int lane = (int)(threadIdx.x & 63u);
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const T u = __shfl_up(v, d);
-        if (lane >= d) v += u;
-    }
-    return v;
-}
-
-// exclusive prefix of a over the threads of a block of NT threads and the block's total; s: NT / 64 entries
-template <class T, int NT> __device__ __forceinline__ void block_excl_scan(T a, T *s, T &pre, T &tot)
-{
-    constexpr int NW = NT / 64;
-    const int lane = (int)(threadIdx.x & 63u), w = (int)(threadIdx.x >> 6);
-    const T ia = wave_incl_scan(a);
-    __syncthreads(); // (the array may still be read from the previous call)
-    if (lane == 63) s[w] = ia;
-    __syncthreads();
-    T wa = 0, ta = 0;
-#pragma unroll
-    for (int k = 0; k < NW; ++k) {
-        const T x = s[k];
-        if (k < w) wa += x;
-        ta += x;
-    }
-    pre = wa + ia - a;
-    tot = ta;
-}
 
 // 0x80 in every byte of w that equals c (exact: no carry between bytes)
 __device__ __forceinline__ uint32_t eq_bytes(uint32_t w, uint32_t c4)
@@ -332,95 +298,41 @@ __global__ __launch_bounds__(REC_THREADS) void parse_rec_apply(const uint8_t *__
     }
 }
 
-// bytes [lo, hi) of a 16-byte piece that lie in its dword j, as a mask of 0xff bytes
-__device__ __forceinline__ uint32_t byte_range_mask(int lo, int hi, int j)
-{
-    int a = lo - 4 * j, b = hi - 4 * j;
-    a = a < 0 ? 0 : (a > 4 ? 4 : a);
-    b = b < 0 ? 0 : (b > 4 ? 4 : b);
-    if (b <= a) return 0u;
-    const uint32_t mb = b == 4 ? 0xffffffffu : ((1u << (8 * b)) - 1u);
-    const uint32_t ma = (1u << (8 * a)) - 1u; // a < 4 here
-    return mb & ~ma;
-}
+// a piece of the two arenas
+struct ParsePiece {
+    const uint8_t *__restrict__ text;
+    const uint32_t *__restrict__ line_start, *__restrict__ offset;
+    uint8_t *__restrict__ out_seq, *__restrict__ out_qual;
+    uint32_t as[4], aq[4];
+
+    __device__ __forceinline__ void clear() { as[0] = as[1] = as[2] = as[3] = aq[0] = aq[1] = aq[2] = aq[3] = 0; }
+    __device__ __forceinline__ uint2 record(uint32_t k) const { return make_uint2(offset[k], offset[(size_t)k + 1]); }
+    __device__ __forceinline__ void fill(const uint2 &r, uint32_t k, unsigned long long, int d, int e, unsigned long long pos)
+    {
+        const uint4 ls = reinterpret_cast<const uint4 *>(line_start)[k];
+        const uint32_t w0 = (uint32_t)pos - r.x; // position in the record of byte d
+        const U128u vs = *reinterpret_cast<const U128u *>(text + ((size_t)ls.y + w0) - d);
+        const U128u vq = *reinterpret_cast<const U128u *>(text + ((size_t)ls.w + w0) - d);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint32_t m = (d == 0 && e == 16) ? 0xffffffffu : byte_mask(range_bits(d, e), j);
+            as[j] = merge_bytes(as[j], vs.w[j], m);
+            aq[j] = merge_bytes(aq[j], vq.w[j], m);
+        }
+    }
+    __device__ __forceinline__ void store(unsigned long long o) const
+    {
+        *reinterpret_cast<uint4 *>(out_seq + o) = make_uint4(as[0], as[1], as[2], as[3]);
+        *reinterpret_cast<uint4 *>(out_qual + o) = make_uint4(aq[0], aq[1], aq[2], aq[3]);
+    }
+};
 
 __global__ __launch_bounds__(GATHER_THREADS) void parse_gather(const uint8_t *__restrict__ text, const uint32_t *__restrict__ line_start, const uint32_t *__restrict__ offset,
                                                                const faqcs_parse_info *__restrict__ info, uint8_t *__restrict__ out_seq, uint8_t *__restrict__ out_qual)
 {
     if (info->overflow) return;
-    const unsigned long long n_bytes = info->n_bytes; // < 2^32
-    const uint32_t n_rec = info->n_reads;
-    const uint32_t lane = threadIdx.x & 63u;
-    const unsigned long long wave = (unsigned long long)blockIdx.x * (GATHER_THREADS / 64) + uniu(threadIdx.x >> 6);
-    const unsigned long long n_waves = (unsigned long long)gridDim.x * (GATHER_THREADS / 64);
-    for (unsigned long long span = wave; span * SPAN_BYTES < n_bytes; span += n_waves) {
-        const unsigned long long o0 = span * SPAN_BYTES;
-        // the record under the span's first byte: the largest k with offset[k] <= o0 (offset[n_rec] == n_bytes > o0)
-        uint32_t kw = 0;
-        {
-            uint32_t lo = 0, hi = n_rec; // offset[lo] <= o0 < offset[hi]
-            while (hi - lo > 1) {
-                const uint32_t mid = lo + ((hi - lo) >> 1);
-                if (offset[mid] <= (uint32_t)o0) lo = mid; else hi = mid;
-            }
-            kw = uniu(lo);
-        }
-        for (uint32_t it = 0; it < SPAN_ITERS; ++it) {
-            const unsigned long long ow = o0 + (unsigned long long)it * WAVE_BYTES;
-            if (ow >= n_bytes) break;
-            const unsigned long long o = ow + lane * 16u;
-            const bool active = o < n_bytes;
-            const uint32_t o32 = (uint32_t)o;
-            // this lane's record: kw + (how many of offset[kw + 1 ..] are <= o)
-            const uint32_t jx = kw + 1u + lane;
-            const uint32_t offv = offset[(jx > n_rec || jx < kw) ? n_rec : jx];
-            uint32_t c = 0;
-#pragma unroll
-            for (uint32_t step = 32; step; step >>= 1) {
-                const uint32_t v = (uint32_t)__shfl((int)offv, (int)(c + step - 1u));
-                if (v <= o32) c += step;
-            }
-            uint32_t k = kw + c;
-            const uint32_t v63 = (uint32_t)__builtin_amdgcn_readlane((int)offv, 63);
-            if (active && c == 63u && v63 <= o32) {
-                // more than 64 records end inside this wave's KiB (records of a few bases, empty ones): a search of its own
-                uint32_t lo = kw + 64u, hi = n_rec; // offset[lo] <= o < offset[hi]
-                while (hi - lo > 1) {
-                    const uint32_t mid = lo + ((hi - lo) >> 1);
-                    if (offset[mid] <= o32) lo = mid; else hi = mid;
-                }
-                k = lo;
-            }
-            if (!active) k = kw;
-            if (active) {
-                const unsigned long long oend = (o + 16u < n_bytes) ? o + 16u : n_bytes;
-                uint32_t as[4] = {0, 0, 0, 0}, aq[4] = {0, 0, 0, 0};
-                unsigned long long pos = o;
-                while (pos < oend) { // (k < n_rec while pos < n_bytes == offset[n_rec])
-                    const uint32_t rb = offset[k], re = offset[(size_t)k + 1];
-                    if ((unsigned long long)re > pos) {
-                        const unsigned long long segend = (unsigned long long)re < oend ? (unsigned long long)re : oend;
-                        const int d = (int)(pos - o), e = (int)(segend - o); // bytes [d, e) of the piece
-                        const uint4 ls = reinterpret_cast<const uint4 *>(line_start)[k];
-                        const uint32_t w0 = (uint32_t)pos - rb; // position in the record of byte d
-                        const U128u vs = *reinterpret_cast<const U128u *>(text + ((size_t)ls.y + w0) - d);
-                        const U128u vq = *reinterpret_cast<const U128u *>(text + ((size_t)ls.w + w0) - d);
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            const uint32_t m = (d == 0 && e == 16) ? 0xffffffffu : byte_range_mask(d, e, j);
-                            as[j] = (as[j] & ~m) | (vs.w[j] & m);
-                            aq[j] = (aq[j] & ~m) | (vq.w[j] & m);
-                        }
-                        pos = segend;
-                    }
-                    if ((unsigned long long)re <= pos) ++k;
-                }
-                *reinterpret_cast<uint4 *>(out_seq + o) = make_uint4(as[0], as[1], as[2], as[3]);
-                *reinterpret_cast<uint4 *>(out_qual + o) = make_uint4(aq[0], aq[1], aq[2], aq[3]);
-            }
-            kw = (uint32_t)__builtin_amdgcn_readlane((int)k, 63); // a lower bound for the next KiB
-        }
-    }
+    ParsePiece p{text, line_start, offset, out_seq, out_qual, {}, {}};
+    for_each_piece_segment(offset, info->n_reads, info->n_bytes, p);
 }
 
 size_t text_tiles(unsigned long long n_text) { return (size_t)((n_text + TEXT_TILE - 1) / TEXT_TILE); }
@@ -493,13 +405,9 @@ hipError_t faqcs_launch_parse_records(const uint8_t *text, unsigned long long n_
 hipError_t faqcs_launch_parse_gather(const uint8_t *text, unsigned long long n_text, const faqcs_parse_out *out, const void *scratch, int n_cu, hipStream_t st)
 {
     const Scratch s = carve(const_cast<void *>(scratch), n_text, nullptr);
-    // an arena cannot take more than min(capacity, half of the text) bytes; the grid is cut to that, the waves stride over the spans
-    unsigned long long most = out->capacity_bytes < n_text / 2 ? out->capacity_bytes : n_text / 2;
-    const unsigned long long spans = (most + SPAN_BYTES - 1) / SPAN_BYTES;
-    unsigned long long grid = (spans + GATHER_THREADS / 64 - 1) / (GATHER_THREADS / 64);
-    const unsigned long long cap = (unsigned long long)(n_cu > 0 ? n_cu : 256) * 8;
-    if (grid > cap) grid = cap;
+    // an arena cannot take more than min(capacity, half of the text) bytes
+    const unsigned grid = gather_grid(out->capacity_bytes < n_text / 2 ? out->capacity_bytes : n_text / 2, n_cu);
     if (!grid) return hipSuccess;
-    hipLaunchKernelGGL(parse_gather, dim3((unsigned)grid), dim3(GATHER_THREADS), 0, st, text, s.line_start, out->offset, out->info, out->seq, out->qual);
+    hipLaunchKernelGGL(parse_gather, dim3(grid), dim3(GATHER_THREADS), 0, st, text, s.line_start, out->offset, out->info, out->seq, out->qual);
     return hipGetLastError();
 }
