@@ -5,8 +5,11 @@
 // architecture: per input file an I/O thread cuts the (gz) byte stream into blocks of 32 768 records and a pool of
 // parser threads turns them into pinned structure-of-arrays buffers (the reference's trim() granularity,
 // delivered in file order); the main thread pairs them up and submits
-// them through the pipelined C ABI (faqcs_submit_async), and a writer thread emits the survivors in input
-// order while later buffers are parsed and trimmed.  The per-read hot path runs ONLY on the GPU library.
+// them through the pipelined C ABI (faqcs_submit_async), and a gate thread, a pool of formatters and one committer
+// per mate file emit the survivors in input order while later buffers are parsed and trimmed.  That is
+// process_streamed(); plain regular files take process_mapped() instead.  Each of the two states the reference's
+// buffer loop once, for paired and for unpaired input (b2 == nullptr), and both call the same per-buffer rules:
+// pair_check(), Run::preconditions(), Run::route(), render_read().  The per-read hot path runs ONLY on the GPU library.
 #include <zlib.h>
 
 #include <fcntl.h>
@@ -829,6 +832,49 @@ struct OutFile {
     void close() { flush(); if (f) fclose(f); f = nullptr; }
 };
 
+// one surviving record, with the reference's byte edits (trim.cpp:390-403,516-525,1191-1216; fastq.cpp:127-138), rendered at o:
+// deflen + 2 * res.len + 5 bytes (def \n seq \n + \n qual \n); returns their end
+char *render_read(const faqcs_params &prm, const RecBuf *b, uint32_t i, char *o)
+{
+    const faqcs_read_result &x = b->res[i];
+    const uint32_t ro = b->off[i], len = b->off[i + 1] - ro;
+    const uint32_t dl = b->deflen(i);
+    memcpy(o, b->def(i), dl); o += dl; *o++ = '\n';
+    const uint8_t *sp = b->seq + ro, *qp = b->qual + ro;
+    if (prm.replace_to_N_q == 0 && prm.input_quality_offset == prm.output_quality_offset && len && sp[0] != 'N' && sp[len - 1] != 'N') {
+        // no byte of this record is edited (trim.cpp:390-403,516-525,1191-1216): copy the kept window
+        memcpy(o, sp + x.start, x.len); o += x.len; memcpy(o, "\n+\n", 3); o += 3;
+        memcpy(o, qp + x.start, x.len); o += x.len; *o++ = '\n';
+        return o;
+    }
+    uint8_t *so = (uint8_t *)o, *qo = (uint8_t *)o + x.len + 3;
+    faqcs_apply_edits(&prm, sp, qp, len, &x, so, qo); // (the edited window straight into the record)
+    memcpy(o + x.len, "\n+\n", 3);
+    o += 2 * (size_t)x.len + 3; *o++ = '\n';
+    return o;
+}
+
+// FaQCs.cpp:370-389 on the buffers of a pair: mate ids, then equal counts.  Returns the text of the error the reference throws (empty:
+// the buffers pair up) and sets `note` to the line it prints first
+std::string pair_check(const RecBuf *b1, const RecBuf *b2, std::string &note)
+{
+    const uint32_t n = std::min(b1->n, b2->n);
+    for (uint32_t i = 0; i < n; ++i) {
+        const char *d1 = b1->def(i), *d2 = b2->def(i);
+        const size_t l1 = id_len(d1, b1->deflen(i)), l2 = id_len(d2, b2->deflen(i));
+        if (l1 != l2 || memcmp(d1, d2, l1) != 0) {
+            note = "Read one id (" + std::string(d1, l1) + ")\ndoes not match\nread two id (" + std::string(d2, l2) + ")\n";
+            return "FaQCs.cpp:trim: I/O error";
+        }
+    }
+    if (b1->n != b2->n) {
+        const RecBuf *lng = b1->n > b2->n ? b1 : b2;
+        note = std::string("Did not find a match to read ") + (b1->n > b2->n ? "one: " : "two: ") + std::string(lng->def(n), lng->deflen(n)) + "\n";
+        return "FaQCs.cppI/O error"; // (the reference's own text)
+    }
+    return std::string();
+}
+
 struct Run {
     Opt &opt;
     faqcs_ctx *ctx = nullptr;            // == ctxs[0]: owns the k-mer table
@@ -910,7 +956,7 @@ struct Run {
         }
         return epoch;
     }
-    // end of a process_paired() / process_unpaired() pass (FaQCs.cpp:518-537): the points taken during the pass get their values,
+    // end of a paired or an unpaired pass (the reference's process_paired() / process_unpaired(), FaQCs.cpp:518-537): the points taken during the pass get their values,
     // the count histograms of the owners' tables are merged, the tables restart
     // A buffer's outbox is forwarded to the owners just before ITS device gets its next buffer (or at the end of the pass), not right behind
     // its own submission: faqcs_kmer_forward waits for the device's stream, and by then the other devices have had their buffers -- the
@@ -993,24 +1039,25 @@ struct Run {
         check(faqcs_submit_async(ctxs[b->dev], &bt, b->res, &b->ticket));
         if (kmer_multi) { kmer_fwd_pending.resize(ctxs.size(), 0); kmer_fwd_pending[(size_t)b->dev] = 1; }
     }
-    // writes one surviving record with the reference's byte edits (trim.cpp:390-403,516-525,1191-1216; fastq.cpp:127-138)
-    void write_read(OutFile &f, const RecBuf *b, uint32_t i, std::string &s, std::string &q)
+    // The host's part of one trim() call on a pair of buffers in input order (b2 == nullptr: on one unpaired buffer), FaQCs.cpp:261-277,
+    // 393-414,608-612,668-683: the buffers' own errors, the quality offset, the NextSeq rule.  True = this is the input's last buffer.
+    // The context(s) and the submission follow at the caller, behind its own time marks.
+    bool preconditions(const RecBuf *b1, const RecBuf *b2, bool &check_for_next_seq)
     {
-        const faqcs_read_result &x = b->res[i];
-        const uint32_t o = b->off[i], len = b->off[i + 1] - o;
-        const size_t dl = b->deflen(i), kept = x.len;
-        char *d = f.room(dl + 2 * kept + 5); // def \n seq \n + \n qual \n
-        memcpy(d, b->def(i), dl); d += dl; *d++ = '\n';
-        const uint8_t *sp = b->seq + o, *qp = b->qual + o;
-        if (prm.replace_to_N_q == 0 && prm.input_quality_offset == prm.output_quality_offset && len && sp[0] != 'N' && sp[len - 1] != 'N') {
-            // no byte of this record is edited (trim.cpp:390-403,516-525,1191-1216): copy the kept window
-            memcpy(d, sp + x.start, kept); d += kept; memcpy(d, "\n+\n", 3); d += 3; memcpy(d, qp + x.start, kept); d += kept; *d++ = '\n';
-        } else {
-            (void)s; (void)q;
-            faqcs_apply_edits(&prm, sp, qp, len, &x, (uint8_t *)d, (uint8_t *)d + kept + 3); // (the edited window straight into the record)
-            d += kept; memcpy(d, "\n+\n", 3); d += 3 + kept; *d++ = '\n';
+        if (!b1->error.empty()) throw Fatal(b1->error);
+        if (b2 && !b2->error.empty()) throw Fatal(b2->error);
+        if (in_off == AUTO_OFFSET) { // FaQCs.cpp:261-270,393-402
+            in_off = detect(b1);
+            if (b2 && in_off != detect(b2)) { fprintf(stderr, "Inconsistent quality offset detection between reads one and two\n"); throw Fatal("FaQCs.cpp:process_paired: I/O Error"); }
         }
-        f.n += dl + 2 * kept + 5;
+        if (b1->eof || check_for_next_seq) { nextseq_check(b1); check_for_next_seq = false; } // Q16: also on the last buffer
+        return b1->eof;
+    }
+    // writes one surviving record with the reference's byte edits (render_read)
+    void write_read(OutFile &f, const RecBuf *b, uint32_t i)
+    {
+        char *d = f.room(b->deflen(i) + 2 * (size_t)b->res[i].len + 5); // def \n seq \n + \n qual \n
+        f.n += (size_t)(render_read(prm, b, i, d) - d);
     }
     static void write_raw(OutFile &f, const RecBuf *b, uint32_t i)
     {
@@ -1018,12 +1065,27 @@ struct Run {
         f.put(b->def(i), b->deflen(i)); f.put("\n", 1);
         f.put((const char *)b->seq + o, len); f.put("\n+\n", 3); f.put((const char *)b->qual + o, len); f.put("\n", 1);
     }
+    // Where record i of a pair of buffers goes (b2 == nullptr: of one unpaired buffer), FaQCs.cpp:300-360,435-495,640-655,700-716: both mates valid -> the
+    // mate files and the PAIRED_* counts; one valid -> the singletons; invalid -> the discards, as read, when there is such a file
+    // (fdisc != nullptr).  Singletons and discards are written here.  True = the caller owes the record(s) to the mate file(s): the mapped
+    // gate sizes them for its formatters, the streaming formatter renders them.  --qc_only counts and writes nothing.
+    bool route(const RecBuf *b1, const RecBuf *b2, uint32_t i, OutFile &fu, OutFile *fdisc, uint64_t &pair_reads, uint64_t &pair_bases)
+    {
+        const bool v1 = b1->res[i].flags & FAQCS_F_VALID, v2 = !b2 || (b2->res[i].flags & FAQCS_F_VALID);
+        if (v1 && v2) {
+            if (b2) { pair_reads += 2; pair_bases += b1->res[i].len + b2->res[i].len; }
+            return !opt.qc_only;
+        }
+        if (opt.qc_only) return false;
+        if (b2) { if (v1) write_read(fu, b1, i); else if (v2) write_read(fu, b2, i); }
+        if (fdisc) { if (!v1) write_raw(*fdisc, b1, i); if (b2 && !v2) write_raw(*fdisc, b2, i); }
+        return false;
+    }
 };
 
 struct Work {
     RecBuf *b1 = nullptr, *b2 = nullptr;
     bool last = false;
-    std::shared_ptr<std::atomic<int>> left; // writers that still read the pair's buffers
 };
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1031,7 +1093,7 @@ struct Work {
 // The streaming path above moves every byte through one I/O thread per file (gzread -> line count -> block -> parser), which
 // tops out near 1.3 GB/s per file; here the input is memory-mapped, an index of the 32 768-record buffers is built by
 // counting newlines in parallel, a pool of parser threads fills pinned structure-of-arrays buffers straight from the mapping
-// (deflines stay there), and a pool of formatter threads renders the survivors of finished buffers and pwrite()s them at
+// (deflines stay there), and a pool of formatter threads renders the survivors of finished buffers into the output files' mappings, at
 // offsets the gate thread hands out in input order.  Same reference semantics, same C ABI underneath.
 // ---------------------------------------------------------------------------------------------------------
 struct MapFile {
@@ -1198,26 +1260,23 @@ void parse_range(const char *base, size_t b0, size_t b1, bool eof, RecBuf *b)
     }
 }
 
-struct FastTask { const RecBuf *mine = nullptr, *b1 = nullptr, *b2 = nullptr; char *dst = nullptr; size_t size = 0; int pair_slot = -1; int fd = -1; off_t off = 0; };
+struct FastTask { const RecBuf *mine = nullptr, *b1 = nullptr, *b2 = nullptr; char *dst = nullptr; size_t size = 0; int pair_slot = -1; };
 
-// one survivor rendered into memory: the bytes Run::write_read() would put
-char *render_read(const faqcs_params &prm, const RecBuf *b, uint32_t i, char *o)
+// An output file that cannot be opened (FaQCs.cpp:188-223, :560-579): the reference's line, then the error for its catch in main()
+static void open_output(OutFile &f, const std::string &path, const char *what)
 {
-    const faqcs_read_result &x = b->res[i];
-    const uint32_t ro = b->off[i], len = b->off[i + 1] - ro;
-    const uint32_t dl = b->deflen(i);
-    memcpy(o, b->def(i), dl); o += dl; *o++ = '\n';
-    const uint8_t *sp = b->seq + ro, *qp = b->qual + ro;
-    if (prm.replace_to_N_q == 0 && prm.input_quality_offset == prm.output_quality_offset && len && sp[0] != 'N' && sp[len - 1] != 'N') {
-        memcpy(o, sp + x.start, x.len); o += x.len; memcpy(o, "\n+\n", 3); o += 3;
-        memcpy(o, qp + x.start, x.len); o += x.len; *o++ = '\n';
-        return o;
+    try { f.open(path); } catch (Fatal &) { fprintf(stderr, "Unable to open %s for writing %s\n", path.c_str(), what); throw; }
+}
+// The same on the streaming path.  The input readers are running by then and may sit on their queues, so the process leaves here as the
+// other error paths of process_streamed() do (unwinding past a Source whose threads run would end in std::terminate).
+static void open_output_or_leave(OutFile &f, const std::string &path, const char *what)
+{
+    try { open_output(f, path, what); }
+    catch (Fatal &e) {
+        fprintf(stderr, "Caught the error %s\n", e.what());
+        fflush(nullptr);
+        _exit(EXIT_FAILURE);
     }
-    uint8_t *so = (uint8_t *)o, *qo = (uint8_t *)o + x.len + 3;
-    faqcs_apply_edits(&prm, sp, qp, len, &x, so, qo);
-    memcpy(o + x.len, "\n+\n", 3);
-    o += 2 * (size_t)x.len + 3; *o++ = '\n';
-    return o;
 }
 
 // FaQCs.cpp:153-538 (paired == true) and :540-757 (paired == false) on mapped inputs
@@ -1258,14 +1317,14 @@ void process_mapped(Run &r, bool paired)
     const unsigned hw = std::max(2u, opt.num_thread ? opt.num_thread : std::thread::hardware_concurrency());
     // parser / formatter threads: a sixth of the host's threads each, at most 16.  The cap is MEASURED, not a leftover (VERDICT r4 asked for it
     // to be lifted on the "256-thread host"): 40 + 40 threads take 2.1 s where 16 + 16 take 1.17 s on 14.3 M pairs in tmpfs, and helper threads
-    // that make the output pages ahead of the formatters (madvise(MADV_POPULATE_WRITE), below) cost 0.9 s more than they save
+    // that made the output pages ahead of the formatters (madvise(MADV_POPULATE_WRITE)) cost 0.9 s more than they save
     // (profiles/r5a/e2e_threads.txt).  The reason, found afterwards: the GPU boxes show 256 hardware threads and allow the process SIXTEEN CPUs
     // (cgroup cpu.max 1600000 100000; 16 threads of zlib crc32 saturate the box, profiles/r5a/cpu_quota.txt) -- every end-to-end figure of this
-    // repository is bound by 16 cores, not 256.  FAQCS_MI_PARSERS / FAQCS_MI_FORMATTERS / FAQCS_MI_PREFAULTERS override.
+    // repository is bound by 16 cores, not 256.  FAQCS_MI_PARSERS / FAQCS_MI_FORMATTERS override (the prefault helpers
+    // and their FAQCS_MI_PREFAULTERS were removed; the runs that decided it stay in profiles/r5a/).
     auto env_u = [](const char *name, unsigned dflt) { const char *e = getenv(name); const int v = e ? atoi(e) : 0; return v > 0 ? (unsigned)v : dflt; };
     const unsigned n_parse = env_u("FAQCS_MI_PARSERS", std::min(16u, std::max(2u, hw / 6)));
     const unsigned n_format = env_u("FAQCS_MI_FORMATTERS", std::min(16u, std::max(2u, hw / 6)));
-    const unsigned n_prefault = getenv("FAQCS_MI_PREFAULTERS") ? (unsigned)std::max(0, atoi(getenv("FAQCS_MI_PREFAULTERS"))) : 0u;
     std::vector<size_t> start[2];
     for (int s = 0; s < nsrc; ++s) start[s] = index_buffers(mf[s], std::min(32u, hw));
     tmark("inputs mapped and indexed");
@@ -1294,46 +1353,9 @@ void process_mapped(Run &r, bool paired)
             if (m == MAP_FAILED) throw Fatal("I/O error");
             out_map[s] = (char *)m;
         }
-        auto open_or_say = [](OutFile &f, const std::string &p, const char *what) { // FaQCs.cpp:204-223, :569-579
-            try { f.open(p); } catch (Fatal &) { fprintf(stderr, "Unable to open %s for writing %s\n", p.c_str(), what); throw; }
-        };
-        if (paired) open_or_say(fu, opt.outu, "unpaired sequences");
-        if (!opt.outd.empty()) open_or_say(fdisc, opt.outd, "discarded sequences");
+        if (paired) open_output(fu, opt.outu, "unpaired sequences");
+        if (!opt.outd.empty()) open_output(fdisc, opt.outd, "discarded sequences");
     }
-    // (Off by default, FAQCS_MI_PREFAULTERS=n: measured slower, see above.)  The pages of the output mappings made (allocated, zeroed,
-    // mapped) AHEAD of the formatters by helper threads, slice by slice in file order -- madvise(MADV_POPULATE_WRITE) --, so that a
-    // formatter's stores do not fault one 4 KB page at a time.
-    std::atomic<bool> prefault_stop{false};
-    std::atomic<size_t> prefault_next{0};
-    std::vector<std::thread> prefaulters;
-    struct Slice { char *p; size_t len; };
-    std::vector<Slice> prefault_slices; // in the order the formatters will reach them: the two files alternate
-    {
-        constexpr size_t SLICE = 16u << 20;
-        size_t at[2] = {0, 0};
-        for (bool more = true; more;) {
-            more = false;
-            for (int s = 0; s < nsrc; ++s)
-                if (out_map[s] && at[s] < out_cap[s]) {
-                    const size_t len = std::min(SLICE, out_cap[s] - at[s]);
-                    prefault_slices.push_back(Slice{out_map[s] + at[s], len});
-                    at[s] += len; more = true;
-                }
-        }
-        for (unsigned t = 0; !prefault_slices.empty() && t < n_prefault; ++t)
-            prefaulters.emplace_back([&] {
-                for (;;) {
-                    const size_t i = prefault_next.fetch_add(1);
-                    if (i >= prefault_slices.size() || prefault_stop) return;
-#ifdef MADV_POPULATE_WRITE
-                    if (madvise(prefault_slices[i].p, prefault_slices[i].len, MADV_POPULATE_WRITE) != 0) return;
-#else
-                    if (madvise(prefault_slices[i].p, prefault_slices[i].len, 23) != 0) return; // (MADV_POPULATE_WRITE, Linux 5.14)
-#endif
-                }
-            });
-    }
-    struct PrefaultJoin { std::atomic<bool> &stop; std::vector<std::thread> &v; ~PrefaultJoin() { stop = true; for (auto &t : v) if (t.joinable()) t.join(); } } prefault_join{prefault_stop, prefaulters};
 
     // ---- buffers, parser pool, ordered delivery ----------------------------------------------------------------
     const int NBUF = 6 + (int)n_parse;
@@ -1349,27 +1371,7 @@ void process_mapped(Run &r, bool paired)
     std::atomic<bool> failed{false};
     std::string werr;
 
-    auto pair_check = [&](Slot &sl) { // FaQCs.cpp:370-389: mate ids, then equal counts; the messages are printed by the main thread in order
-        const RecBuf *b1 = sl.b[0], *b2 = sl.b[1];
-        const uint32_t n = std::min(b1->n, b2->n);
-        for (uint32_t i = 0; i < n; ++i) {
-            const char *d1 = b1->def(i), *d2 = b2->def(i);
-            const size_t l1 = id_len(d1, b1->deflen(i)), l2 = id_len(d2, b2->deflen(i));
-            if (l1 != l2 || memcmp(d1, d2, l1) != 0) {
-                char msg[1024];
-                snprintf(msg, sizeof(msg), "Read one id (%.*s)\ndoes not match\nread two id (%.*s)\n", (int)l1, d1, (int)l2, d2);
-                sl.pair_note = msg; sl.pair_error = "FaQCs.cpp:trim: I/O error";
-                return;
-            }
-        }
-        if (b1->n != b2->n) {
-            const RecBuf *lng = b1->n > b2->n ? b1 : b2;
-            char msg[1024];
-            snprintf(msg, sizeof(msg), "Did not find a match to read %s: %.*s\n", b1->n > b2->n ? "one" : "two", (int)lng->deflen(n), lng->def(n));
-            sl.pair_note = msg; sl.pair_error = "FaQCs.cppI/O error";
-        }
-    };
-    std::mutex tm_m; double t_parse_wait = 0, t_parse_work = 0, t_fmt_render = 0, t_fmt_write = 0, t_fmt_idle = 0;
+    std::mutex tm_m; double t_parse_wait = 0, t_parse_work = 0, t_fmt_render = 0, t_fmt_idle = 0;
     auto parser = [&] {
         double w_wait = 0, w_work = 0;
         struct Acc { std::mutex &m; double &a, &b, &x, &y; ~Acc() { std::lock_guard<std::mutex> l(m); a += x; b += y; } } acc{tm_m, t_parse_wait, t_parse_work, w_wait, w_work};
@@ -1398,7 +1400,7 @@ void process_mapped(Run &r, bool paired)
             bool complete = nsrc == 1;
             if (nsrc == 2) {
                 if (k >= nbuf[1 - s]) complete = false;                     // no partner buffer: the pair test of an earlier pair fails first
-                else if (sl.parsed.fetch_add(1) == 1) { pair_check(sl); complete = true; }
+                else if (sl.parsed.fetch_add(1) == 1) { sl.pair_error = pair_check(sl.b[0], sl.b[1], sl.pair_note); complete = true; } // (printed by the main thread, in input order)
             }
             if (complete) { { std::lock_guard<std::mutex> l(rm); pair_ready[k] = 1; } rcv.notify_all(); }
         }
@@ -1438,11 +1440,11 @@ void process_mapped(Run &r, bool paired)
     Queue<FastTask> fq;
     std::atomic<size_t> tasks_out{0};
     auto release_pair = [&](size_t k) { if (refs[k].left.fetch_sub(1) == 1) for (int s = 0; s < nsrc; ++s) if (refs[k].b[s]) give_back(s, refs[k].b[s]); };
-    static const bool out_pwrite = [] { const char *e = getenv("FAQCS_MI_OUT_PWRITE"); return e && atoi(e) != 0; }();
+    // The formatters store into the files' mappings.  Rendering into a private buffer and one pwrite() per task (FAQCS_MI_OUT_PWRITE) was
+    // measured at +-40 % either way and removed; the runs are in profiles/r6j/e2e_pwrite_ab.txt, the finding in DESIGN 8.
     auto formatter = [&] {
-        double w_r = 0, w_w = 0, w_i = 0;
-        std::vector<char> local;
-        struct Acc3 { std::mutex &m; double &a, &b, &c, &x, &y, &z; ~Acc3() { std::lock_guard<std::mutex> l(m); a += x; b += y; c += z; } } acc{tm_m, t_fmt_render, t_fmt_write, t_fmt_idle, w_r, w_w, w_i};
+        double w_r = 0, w_i = 0;
+        struct Acc { std::mutex &m; double &a, &b, &x, &y; ~Acc() { std::lock_guard<std::mutex> l(m); a += x; b += y; } } acc{tm_m, t_fmt_render, t_fmt_idle, w_r, w_i};
         for (;;) {
             const double tf0 = now_s();
             FastTask t = fq.pop();
@@ -1450,24 +1452,11 @@ void process_mapped(Run &r, bool paired)
             w_i += tf1 - tf0;
             if (!t.mine) return;
             if (t.size) {
-                // FAQCS_MI_OUT_PWRITE=1: rendered into a buffer of this thread (its pages are there after the first task) and handed to the file by ONE
-                // pwrite, instead of stores into the file's mapping that fault a fresh 4 KB page each (profiles/microbench/tmpfs_write.cpp)
-                char *const dst0 = out_pwrite ? (local.size() < t.size ? (local.resize(t.size + (t.size >> 2)), local.data()) : local.data()) : t.dst;
-                char *o = dst0;
-                for (uint32_t i = 0; i < t.mine->n; ++i)
+                char *o = t.dst;
+                for (uint32_t i = 0; i < t.mine->n; ++i) // (the records Run::route() left to the mate files)
                     if ((t.b1->res[i].flags & FAQCS_F_VALID) && (!t.b2 || (t.b2->res[i].flags & FAQCS_F_VALID))) o = render_read(r.prm, t.mine, i, o);
-                const double tf2 = now_s();
-                w_r += tf2 - tf1;
-                if ((size_t)(o - dst0) != t.size) fail_run("faqcs_mi: internal error, a rendered buffer has the wrong size");
-                else if (out_pwrite) {
-                    size_t done = 0;
-                    while (done < t.size) {
-                        const ssize_t k = pwrite(t.fd, dst0 + done, t.size - done, t.off + (off_t)done);
-                        if (k <= 0) { fail_run("I/O error"); break; }
-                        done += (size_t)k;
-                    }
-                    w_w += now_s() - tf2;
-                }
+                w_r += now_s() - tf1;
+                if ((size_t)(o - t.dst) != t.size) fail_run("faqcs_mi: internal error, a rendered buffer has the wrong size");
             }
             release_pair((size_t)t.pair_slot);
             --tasks_out;
@@ -1481,7 +1470,6 @@ void process_mapped(Run &r, bool paired)
     Queue<GateWork> wq;
     std::atomic<double> t_gate_wait{0.0}, t_gate_loop{0.0};
     std::thread gate([&] {
-        std::string s, q;
         off_t off_out[2] = {0, 0};
         bool cur_last = false;
         try {
@@ -1497,26 +1485,16 @@ void process_mapped(Run &r, bool paired)
                 t_gate_wait = t_gate_wait.load() + (tg1 - tg0);
                 Run::check_read_errors(b1); if (b2) Run::check_read_errors(b2); // trim() throws before anything of the buffer is written
                 size_t sz[2] = {0, 0};
-                for (uint32_t i = 0; i < b1->n; ++i) {
-                    const bool v1 = b1->res[i].flags & FAQCS_F_VALID, v2 = b2 ? (b2->res[i].flags & FAQCS_F_VALID) != 0 : true;
-                    if (v1 && v2) {
-                        if (b2) { r.paired_read_number += 2; r.paired_base_length += b1->res[i].len + b2->res[i].len; }
+                for (uint32_t i = 0; i < b1->n; ++i)
+                    if (r.route(b1, b2, i, fu, fdisc.f ? &fdisc : nullptr, r.paired_read_number, r.paired_base_length)) {
                         sz[0] += b1->deflen(i) + 2 * (size_t)b1->res[i].len + 5;
                         if (b2) sz[1] += b2->deflen(i) + 2 * (size_t)b2->res[i].len + 5;
-                        continue;
                     }
-                    if (opt.qc_only) continue;
-                    if (b2) {
-                        if (v1) r.write_read(fu, b1, i, s, q);
-                        else if (v2) r.write_read(fu, b2, i, s, q);
-                        if (fdisc.f) { if (!v1) Run::write_raw(fdisc, b1, i); if (!v2) Run::write_raw(fdisc, b2, i); }
-                    } else if (fdisc.f) Run::write_raw(fdisc, b1, i);
-                }
                 refs[w.k].b[0] = b1; refs[w.k].b[1] = b2;
                 refs[w.k].left = opt.qc_only ? 1 : nsrc + 1;
                 if (!opt.qc_only)
                     for (int m = 0; m < nsrc; ++m) {
-                        FastTask t; t.mine = m ? b2 : b1; t.b1 = b1; t.b2 = b2; t.dst = out_map[m] + off_out[m]; t.fd = fd_out[m]; t.off = off_out[m]; t.size = sz[m]; t.pair_slot = (int)w.k;
+                        FastTask t; t.mine = m ? b2 : b1; t.b1 = b1; t.b2 = b2; t.dst = out_map[m] + off_out[m]; t.size = sz[m]; t.pair_slot = (int)w.k;
                         off_out[m] += (off_t)sz[m]; out_len[m] = (size_t)off_out[m];
                         ++tasks_out;
                         fq.push(t);
@@ -1544,16 +1522,9 @@ void process_mapped(Run &r, bool paired)
             if (failed) { GateWork w; w.stop = true; wq.push(w); break; }
             Slot &sl = slots[k];
             RecBuf *b1 = sl.b[0], *b2 = nsrc == 2 ? sl.b[1] : nullptr;
-            if (!sl.pair_note.empty()) fputs(sl.pair_note.c_str(), stderr);
+            if (!sl.pair_note.empty()) fwrite(sl.pair_note.data(), 1, sl.pair_note.size(), stderr);
             if (!sl.pair_error.empty()) throw Fatal(sl.pair_error);
-            if (!b1->error.empty()) throw Fatal(b1->error);
-            if (b2 && !b2->error.empty()) throw Fatal(b2->error);
-            const bool last = b1->eof;
-            if (r.in_off == AUTO_OFFSET) { // FaQCs.cpp:261-270,393-402
-                r.in_off = r.detect(b1);
-                if (b2 && r.in_off != r.detect(b2)) { fprintf(stderr, "Inconsistent quality offset detection between reads one and two\n"); throw Fatal("FaQCs.cpp:process_paired: I/O Error"); }
-            }
-            if (last || check_for_next_seq) { r.nextseq_check(b1); check_for_next_seq = false; } // Q16: also on the last buffer
+            const bool last = r.preconditions(b1, b2, check_for_next_seq);
             if (k == 0) tmark("first pair parsed");
             if (warm.joinable()) warm.join();
             r.ensure_ctx();
@@ -1582,13 +1553,11 @@ void process_mapped(Run &r, bool paired)
     for (size_t t = 0; t < formatters.size(); ++t) fq.push(FastTask());
     for (auto &t : formatters) t.join();
     tmark("outputs written");
-    prefault_stop = true;
-    for (auto &t : prefaulters) if (t.joinable()) t.join(); // (before the files are cut to their length)
     { std::lock_guard<std::mutex> l(am); next_k[0] = nbuf[0]; next_k[1] = nbuf[1]; } // (a longer read two file: its surplus buffers were never wanted)
     acv.notify_all();
     for (auto &t : parsers) t.join();
-    if (getenv("FAQCS_MI_TIMING")) fprintf(stderr, "[faqcs_mi] %u parsers: %.3f s parsing, %.3f s waiting for a buffer; %u formatters: %.3f s rendering, %.3f s in pwrite, %.3f s idle (thread-seconds)\n",
-                                           n_parse, t_parse_work, t_parse_wait, n_format, t_fmt_render, t_fmt_write, t_fmt_idle);
+    if (getenv("FAQCS_MI_TIMING")) fprintf(stderr, "[faqcs_mi] %u parsers: %.3f s parsing, %.3f s waiting for a buffer; %u formatters: %.3f s rendering, %.3f s idle (thread-seconds)\n",
+                                           n_parse, t_parse_work, t_parse_wait, n_format, t_fmt_render, t_fmt_idle);
     for (int s = 0; s < nsrc; ++s)
         if (fd_out[s] >= 0) { // (the mapping itself is left to process exit like the pinned buffers: unmapping gigabytes of written pages takes ~50 ms per file)
             if (ftruncate(fd_out[s], (off_t)out_len[s]) != 0) throw Fatal("I/O error");
@@ -1601,86 +1570,72 @@ void process_mapped(Run &r, bool paired)
     r.kmer_finish_pass(); // FaQCs.cpp:518-537
 }
 
-// An output file of the streaming path that cannot be opened (FaQCs.cpp:188-223, :560-579): the reference's line, then its catch in
-// main().  The input readers are running by then and may sit on their queues, so the process leaves here as the other error paths of
-// these functions do (unwinding past a Source whose threads run would end in std::terminate).
-static void open_output_or_leave(OutFile &f, const std::string &path, const char *what)
-{
-    try { f.open(path); }
-    catch (Fatal &e) {
-        fprintf(stderr, "Unable to open %s for writing %s\n", path.c_str(), what);
-        fprintf(stderr, "Caught the error %s\n", e.what());
-        fflush(nullptr);
-        _exit(EXIT_FAILURE);
-    }
-}
-
-// FaQCs.cpp:153-538
-void process_paired(Run &r)
+// FaQCs.cpp:153-538 (paired == true) and :540-757 (paired == false) on inputs that are read as streams (compressed, a pipe, or forced)
+void process_streamed(Run &r, bool paired)
 {
     Opt &opt = r.opt;
-    Source s1, s2;
-    // 32 768-read buffers per input file between its reader and the writers (FAQCS_MI_STREAM_BUFS: 4 ... 64)
+    const int nsrc = paired ? 2 : 1;
+    Source src[2];
+    auto mark = [&](const char *what) { if (paired) tmark(what); }; // (the unpaired pass has never had time marks)
+    // 32 768-read buffers per input file between its reader and the writers (FAQCS_MI_STREAM_BUFS: 4 ... 64).  An unpaired file is read
+    // alone: 16 buffers and twice the parsers
     const int n_stream_bufs = [] { const char *e = getenv("FAQCS_MI_STREAM_BUFS"); const int v = e ? atoi(e) : 0; return v >= 4 && v <= 64 ? v : 12; }();
-    tmark("streaming: opening the inputs");
-    try { s1.start(opt.in1, n_stream_bufs, r.n_parse); } catch (Fatal &) { fprintf(stderr, "Unable to open %s for loading read one sequences\n", opt.in1.c_str()); throw; }
-    try { s2.start(opt.in2, n_stream_bufs, r.n_parse); }
-    catch (Fatal &e) {
-        // (FaQCs.cpp:167-176.  The first file's readers are running and may sit on their queues: leave as the other error paths of this
-        // function do -- unwinding past a Source whose threads run would end in std::terminate, which it did until round 6)
-        fprintf(stderr, "Unable to open %s for loading read two sequences\n", opt.in2.c_str());
-        fprintf(stderr, "Caught the error %s\n", e.what());
-        fflush(nullptr);
-        _exit(EXIT_FAILURE);
-    }
-    tmark("streaming: inputs open, readers running");
-    OutFile f1, f2, fu, fd;
+    const std::string &in1 = paired ? opt.in1 : opt.inu;
+    src[0].alone = !paired;
+    mark("streaming: opening the inputs");
+    try { src[0].start(in1, paired ? n_stream_bufs : 16, paired ? r.n_parse : 2 * r.n_parse); }
+    catch (Fatal &) { fprintf(stderr, "Unable to open %s for loading %s sequences\n", in1.c_str(), paired ? "read one" : "unpaired read"); throw; }
+    if (paired)
+        try { src[1].start(opt.in2, n_stream_bufs, r.n_parse); }
+        catch (Fatal &e) {
+            // (FaQCs.cpp:167-176.  The first file's readers are running and may sit on their queues: leave as the other error paths of this
+            // function do -- unwinding past a Source whose threads run would end in std::terminate, which it did until round 6)
+            fprintf(stderr, "Unable to open %s for loading read two sequences\n", opt.in2.c_str());
+            fprintf(stderr, "Caught the error %s\n", e.what());
+            fflush(nullptr);
+            _exit(EXIT_FAILURE);
+        }
+    mark("streaming: inputs open, readers running");
+    OutFile f[2], fu, fd; // f[0]: mate 1, or the survivors of unpaired input
     if (!opt.qc_only) {
-        open_output_or_leave(f1, opt.out1, "read one sequences"); open_output_or_leave(f2, opt.out2, "read two sequences");
-        open_output_or_leave(fu, opt.outu, "unpaired sequences");
+        if (paired) {
+            open_output_or_leave(f[0], opt.out1, "read one sequences"); open_output_or_leave(f[1], opt.out2, "read two sequences");
+            open_output_or_leave(fu, opt.outu, "unpaired sequences");
+        } else open_output_or_leave(f[0], opt.outu, "unpaired read sequences"); // "wT": truncates the paired pass's singletons (Q17)
         if (!opt.outd.empty()) open_output_or_leave(fd, opt.outd, "discarded sequences");
     }
     // Output side: a gate thread waits for the device and applies the reference's "trim() threw, nothing of this buffer is written"
-    // rule; a small pool of formatters renders a pair of buffers into four texts (mate 1, mate 2, singletons, discards) and hands the
-    // buffers straight back to the readers; two committers write the texts in input order, one per mate file (the singleton and
-    // discard texts go with mate 1).  Until round 6 each mate file was rendered AND written by one thread: with the inflate out of the
-    // way those two threads were what compressed input waited for (76 - 88 % busy, profiles/r6l/e2e_gz_threads.txt).
-    struct Rendered { OutFile t1, t2, tu, td; uint64_t prn = 0, pbl = 0; std::atomic<int> left{0}; };
+    // rule; a small pool of formatters renders a pair of buffers into four texts (mate 1, mate 2, singletons, discards; unpaired input
+    // uses the first and the last) and hands the buffers straight back to the readers; one committer per mate file writes the texts in
+    // input order (the singleton and discard texts go with mate 1).  Until round 6 each mate file was rendered AND written by one thread:
+    // with the inflate out of the way those two threads were what compressed input waited for (76 - 88 % busy,
+    // profiles/r6l/e2e_gz_threads.txt).
+    struct Rendered { OutFile t[2], tu, td; uint64_t prn = 0, pbl = 0; std::atomic<int> left{0}; };
     struct Job { Work w; uint64_t seq = 0; Rendered *out = nullptr; };
     const unsigned n_render = [&] { const char *e = getenv("FAQCS_MI_STREAM_FORMATTERS"); const int v = e ? atoi(e) : 0; return (unsigned)(v >= 1 && v <= 32 ? v : std::max(2, std::min(6, r.n_parse))); }();
     std::vector<Rendered> rendered(n_render + 4);
     Queue<Rendered *> free_r;
-    for (auto &x : rendered) { for (OutFile *o : {&x.t1, &x.t2, &x.tu, &x.td}) o->in_memory = true; free_r.push(&x); }
+    for (auto &x : rendered) { for (OutFile *o : {&x.t[0], &x.t[1], &x.tu, &x.td}) o->in_memory = true; free_r.push(&x); }
     Queue<Work> wq;
     Queue<Job> fq;
     std::mutex cm; std::condition_variable ccv;
-    std::map<uint64_t, Rendered *> done;         // rendered, not yet written by both committers
+    std::map<uint64_t, Rendered *> done;         // rendered, not yet written by every committer
     uint64_t n_jobs = ~0ull;                     // how many there will be (known when the gate has seen the last pair, or an error)
     std::string werr;
     std::atomic<bool> failed{false};
+    auto give_back = [&](const Work &w) { src[0].free_q.push(w.b1); if (w.b2) src[1].free_q.push(w.b2); };
     auto formatter = [&] {
         FaqcsThreadCpu cpu_note("streaming formatter");
-        std::string s, q;
         for (;;) {
             Job j = fq.pop();
             if (!j.out) break;
             Rendered &x = *j.out;
             const RecBuf *b1 = j.w.b1, *b2 = j.w.b2;
-            x.t1.n = x.t2.n = x.tu.n = x.td.n = 0; x.prn = x.pbl = 0;
-            for (uint32_t i = 0; i < b1->n; ++i) {
-                const bool v1 = b1->res[i].flags & FAQCS_F_VALID, v2 = b2->res[i].flags & FAQCS_F_VALID;
-                if (v1 && v2) {
-                    x.prn += 2; x.pbl += b1->res[i].len + b2->res[i].len;
-                    if (!opt.qc_only) { r.write_read(x.t1, b1, i, s, q); r.write_read(x.t2, b2, i, s, q); }
-                    continue;
-                }
-                if (opt.qc_only) continue;
-                if (v1) r.write_read(x.tu, b1, i, s, q);
-                else if (v2) r.write_read(x.tu, b2, i, s, q);
-                if (fd.f) { if (!v1) Run::write_raw(x.td, b1, i); if (!v2) Run::write_raw(x.td, b2, i); }
-            }
-            s1.free_q.push(j.w.b1); s2.free_q.push(j.w.b2); // (the readers have their buffers back before a byte is written)
-            x.left = 2;
+            x.t[0].n = x.t[1].n = x.tu.n = x.td.n = 0; x.prn = x.pbl = 0;
+            for (uint32_t i = 0; i < b1->n; ++i)
+                if (r.route(b1, b2, i, x.tu, fd.f ? &x.td : nullptr, x.prn, x.pbl)) { r.write_read(x.t[0], b1, i); if (b2) r.write_read(x.t[1], b2, i); }
+            give_back(j.w); // (the readers have their buffers back before a byte is written)
+            x.left = nsrc;
             { std::lock_guard<std::mutex> l(cm); done[j.seq] = &x; }
             ccv.notify_all();
         }
@@ -1696,22 +1651,21 @@ void process_paired(Run &r)
                 x = done[seq];
             }
             if (!second) {
-                if (f1.f && x->t1.n) fwrite(x->t1.buf.data(), 1, x->t1.n, f1.f);
+                if (f[0].f && x->t[0].n) fwrite(x->t[0].buf.data(), 1, x->t[0].n, f[0].f);
                 if (fu.f && x->tu.n) fwrite(x->tu.buf.data(), 1, x->tu.n, fu.f);
                 if (fd.f && x->td.n) fwrite(x->td.buf.data(), 1, x->td.n, fd.f);
                 r.paired_read_number += x->prn; r.paired_base_length += x->pbl;
-            } else if (f2.f && x->t2.n) fwrite(x->t2.buf.data(), 1, x->t2.n, f2.f);
+            } else if (f[1].f && x->t[1].n) fwrite(x->t[1].buf.data(), 1, x->t[1].n, f[1].f);
             if (x->left.fetch_sub(1) == 1) {
                 { std::lock_guard<std::mutex> l(cm); done.erase(seq); }
                 free_r.push(x);
             }
         }
     };
-    std::vector<std::thread> formatters;
-    for (unsigned k = 0; k < n_render; ++k) formatters.emplace_back(formatter);
-    std::thread writer1([&] { committer(false); });
-    std::thread writer2([&] { committer(true); });
-    std::thread writer([&] {
+    std::vector<std::thread> pool; // the formatters and the committers
+    for (unsigned k = 0; k < n_render; ++k) pool.emplace_back(formatter);
+    for (int s = 0; s < nsrc; ++s) pool.emplace_back([&committer, s] { committer(s == 1); });
+    std::thread gate([&] {
         FaqcsThreadCpu cpu_note("streaming gate");
         bool cur_last = false; // the pair in hand is the input's last one: nothing follows it in the queue
         uint64_t seq = 0;
@@ -1721,8 +1675,8 @@ void process_paired(Run &r)
                 if (!w.b1) break;
                 cur_last = w.last;
                 Run::check(faqcs_wait(r.ctxs[w.b1->dev], w.b1->ticket));
-                Run::check(faqcs_wait(r.ctxs[w.b2->dev], w.b2->ticket));
-                Run::check_read_errors(w.b1); Run::check_read_errors(w.b2); // trim() throws before anything of the buffer is written
+                if (w.b2) Run::check(faqcs_wait(r.ctxs[w.b2->dev], w.b2->ticket));
+                Run::check_read_errors(w.b1); if (w.b2) Run::check_read_errors(w.b2); // trim() throws before anything of the buffer is written
                 Job j; j.w = w; j.seq = seq++; j.out = free_r.pop(); // (a text set to render into: bounds what is in flight)
                 fq.push(j);
                 if (w.last) break;
@@ -1735,7 +1689,7 @@ void process_paired(Run &r)
             while (!cur_last) {
                 Work w = wq.pop();
                 if (!w.b1) break;
-                s1.free_q.push(w.b1); s2.free_q.push(w.b2);
+                give_back(w);
                 cur_last = w.last;
             }
         }
@@ -1749,178 +1703,35 @@ void process_paired(Run &r)
     try {
         for (;;) {
             if (failed) { wq.push(Work()); break; } // the gate thread met an error of the device (reported below)
-            RecBuf *b1 = s1.pop(), *b2 = s2.pop();
-            const uint32_t n = std::min(b1->n, b2->n);
-            for (uint32_t i = 0; i < n; ++i) { // FaQCs.cpp:383-389
-                const char *d1 = b1->def(i), *d2 = b2->def(i);
-                const size_t l1 = id_len(d1, b1->deflen(i)), l2 = id_len(d2, b2->deflen(i));
-                if (l1 != l2 || memcmp(d1, d2, l1) != 0) {
-                    fprintf(stderr, "Read one id (%.*s)\ndoes not match\nread two id (%.*s)\n", (int)l1, d1, (int)l2, d2);
-                    throw Fatal("FaQCs.cpp:trim: I/O error");
-                }
+            Work w; w.b1 = src[0].pop(); w.b2 = paired ? src[1].pop() : nullptr;
+            if (w.b2) {
+                std::string note;
+                const std::string err = pair_check(w.b1, w.b2, note);
+                if (!err.empty()) { fwrite(note.data(), 1, note.size(), stderr); throw Fatal(err); }
             }
-            if (b1->n != b2->n) { // FaQCs.cpp:370-380
-                const RecBuf *lng = b1->n > b2->n ? b1 : b2;
-                fprintf(stderr, "Did not find a match to read %s: %.*s\n", b1->n > b2->n ? "one" : "two",
-                        (int)lng->deflen(n), lng->def(n));
-                throw Fatal("FaQCs.cppI/O error");
-            }
-            if (!b1->error.empty()) throw Fatal(b1->error);
-            if (!b2->error.empty()) throw Fatal(b2->error);
-            const bool last = b1->eof;
-            if (r.in_off == AUTO_OFFSET) { // FaQCs.cpp:261-270,393-402
-                r.in_off = r.detect(b1);
-                if (r.in_off != r.detect(b2)) { fprintf(stderr, "Inconsistent quality offset detection between reads one and two\n"); throw Fatal("FaQCs.cpp:process_paired: I/O Error"); }
-            }
-            if (last || check_for_next_seq) { r.nextseq_check(b1); check_for_next_seq = false; } // Q16: also on the last buffer
-            if (pair_no == 0) tmark("streaming: first pair of buffers parsed");
+            w.last = r.preconditions(w.b1, w.b2, check_for_next_seq);
+            if (pair_no == 0) mark("streaming: first pair of buffers parsed");
             r.ensure_ctx();
-            if (pair_no == 0) tmark("streaming: device context ready");
-            r.submit(b1, pair_no); r.submit(b2, pair_no);
+            if (pair_no == 0) mark("streaming: device context ready");
+            r.submit(w.b1, pair_no); if (w.b2) r.submit(w.b2, pair_no);
             ++pair_no;
-            if (last) tmark("streaming: last pair of buffers submitted");
-            Work w; w.b1 = b1; w.b2 = b2; w.last = last;
+            if (w.last) mark("streaming: last pair of buffers submitted");
             wq.push(w);
-            if (last) break;
+            if (w.last) break;
         }
     } catch (std::exception &e) { merr = e.what(); wq.push(Work()); }
-    writer.join();
-    for (auto &th : formatters) th.join();
-    writer1.join(); writer2.join();
-    tmark("streaming: paired outputs written");
-    if (!merr.empty() || !werr.empty()) { // unblock the readers, then report like the reference's catch in main()
-        f1.close(); f2.close(); fu.close(); fd.close();
+    gate.join();
+    for (auto &th : pool) th.join();
+    mark("streaming: paired outputs written");
+    if (!merr.empty() || !werr.empty()) { // report like the reference's catch in main()
+        for (OutFile *o : {&f[0], &f[1], &fu, &fd}) o->close();
         fprintf(stderr, "Caught the error %s\n", (!werr.empty() ? werr : merr).c_str());
         _exit(EXIT_FAILURE); // reader / parser threads may be blocked on their queues: leave like the reference's catch in main()
     }
-    s1.stop(); s2.stop();
-    tmark("streaming: readers stopped");
-    f1.close(); f2.close(); fu.close(); fd.close();
-    r.kmer_finish_pass(); // FaQCs.cpp:518-537
-}
-
-// FaQCs.cpp:540-757
-void process_unpaired(Run &r)
-{
-    Opt &opt = r.opt;
-    Source s;
-    s.alone = true;
-    try { s.start(opt.inu, 16, 2 * r.n_parse); } catch (Fatal &) { fprintf(stderr, "Unable to open %s for loading unpaired read sequences\n", opt.inu.c_str()); throw; }
-    OutFile fo, fd;
-    if (!opt.qc_only) { // "wT": truncates process_paired's singletons (Q17)
-        open_output_or_leave(fo, opt.outu, "unpaired read sequences");
-        if (!opt.outd.empty()) open_output_or_leave(fd, opt.outd, "discarded sequences");
-    }
-    // Output side, as in process_paired: a gate waits for the device (trim() throws before anything of its buffer is written), a pool of
-    // formatters renders the buffers and hands them straight back to the reader, one committer writes the texts in input order.
-    struct Rendered { OutFile t, td; };
-    struct Job { Work w; uint64_t seq = 0; Rendered *out = nullptr; };
-    const unsigned n_render = [&] { const char *e = getenv("FAQCS_MI_STREAM_FORMATTERS"); const int v = e ? atoi(e) : 0; return (unsigned)(v >= 1 && v <= 32 ? v : std::max(2, std::min(6, r.n_parse))); }();
-    std::vector<Rendered> rendered(n_render + 4);
-    Queue<Rendered *> free_r;
-    for (auto &x : rendered) { x.t.in_memory = x.td.in_memory = true; free_r.push(&x); }
-    Queue<Work> wq;
-    Queue<Job> fq;
-    std::mutex cm; std::condition_variable ccv;
-    std::map<uint64_t, Rendered *> done;
-    uint64_t n_jobs = ~0ull;
-    std::string werr;
-    std::atomic<bool> failed{false};
-    auto formatter = [&] {
-        FaqcsThreadCpu cpu_note("streaming formatter");
-        std::string sq, qq;
-        for (;;) {
-            Job j = fq.pop();
-            if (!j.out) break;
-            Rendered &x = *j.out;
-            const RecBuf *b = j.w.b1;
-            x.t.n = x.td.n = 0;
-            if (!opt.qc_only)
-                for (uint32_t i = 0; i < b->n; ++i) {
-                    if (b->res[i].flags & FAQCS_F_VALID) r.write_read(x.t, b, i, sq, qq);
-                    else if (fd.f) Run::write_raw(x.td, b, i);
-                }
-            s.free_q.push(j.w.b1);
-            { std::lock_guard<std::mutex> l(cm); done[j.seq] = &x; }
-            ccv.notify_all();
-        }
-    };
-    std::vector<std::thread> formatters;
-    for (unsigned k = 0; k < n_render; ++k) formatters.emplace_back(formatter);
-    std::thread committer([&] {
-        FaqcsThreadCpu cpu_note("streaming committer (writes one mate file in order)");
-        for (uint64_t seq = 0;; ++seq) {
-            Rendered *x;
-            {
-                std::unique_lock<std::mutex> l(cm);
-                ccv.wait(l, [&] { return done.count(seq) != 0 || seq >= n_jobs; });
-                if (seq >= n_jobs) return;
-                x = done[seq];
-                done.erase(seq);
-            }
-            if (fo.f && x->t.n) fwrite(x->t.buf.data(), 1, x->t.n, fo.f);
-            if (fd.f && x->td.n) fwrite(x->td.buf.data(), 1, x->td.n, fd.f);
-            free_r.push(x);
-        }
-    });
-    std::thread writer([&] {
-        FaqcsThreadCpu cpu_note("streaming gate");
-        bool cur_last = false;
-        uint64_t seq = 0;
-        try {
-            for (;;) {
-                Work w = wq.pop();
-                if (!w.b1) break;
-                cur_last = w.last;
-                Run::check(faqcs_wait(r.ctxs[w.b1->dev], w.b1->ticket));
-                Run::check_read_errors(w.b1);
-                Job j; j.w = w; j.seq = seq++; j.out = free_r.pop();
-                fq.push(j);
-                if (w.last) break;
-            }
-        } catch (std::exception &e) {
-            werr = e.what();
-            failed = true;
-            while (!cur_last) { // keep the reader supplied with buffers until the producer has seen the failure
-                Work w = wq.pop();
-                if (!w.b1) break;
-                s.free_q.push(w.b1);
-                cur_last = w.last;
-            }
-        }
-        { std::lock_guard<std::mutex> l(cm); n_jobs = seq; }
-        ccv.notify_all();
-        for (unsigned k = 0; k < n_render; ++k) fq.push(Job());
-    });
-    bool check_for_next_seq = true;
-    std::string merr;
-    uint64_t buf_no = 0;
-    try {
-        for (;;) {
-            if (failed) { wq.push(Work()); break; }
-            RecBuf *b = s.pop();
-            if (!b->error.empty()) throw Fatal(b->error);
-            const bool last = b->eof;
-            if (r.in_off == AUTO_OFFSET) r.in_off = r.detect(b);
-            if (last || check_for_next_seq) { r.nextseq_check(b); check_for_next_seq = false; }
-            r.ensure_ctx();
-            r.submit(b, buf_no++);
-            Work w; w.b1 = b; w.last = last;
-            wq.push(w);
-            if (last) break;
-        }
-    } catch (std::exception &e) { merr = e.what(); wq.push(Work()); }
-    writer.join();
-    for (auto &th : formatters) th.join();
-    committer.join();
-    if (!merr.empty() || !werr.empty()) {
-        fo.close(); fd.close();
-        fprintf(stderr, "Caught the error %s\n", (!werr.empty() ? werr : merr).c_str());
-        _exit(EXIT_FAILURE);
-    }
-    s.stop();
-    fo.close(); fd.close();
-    r.kmer_finish_pass();
+    for (int s = 0; s < nsrc; ++s) src[s].stop();
+    mark("streaming: readers stopped");
+    for (OutFile *o : {&f[0], &f[1], &fu, &fd}) o->close();
+    r.kmer_finish_pass(); // FaQCs.cpp:518-537, :737-756
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -2502,8 +2313,8 @@ static int run_command(int argc, char **argv)
         Run r(opt);
         // uncompressed regular files take the mapped path; gzip members, pipes and FAQCS_MI_STREAMING=1 the streaming one
         const bool streaming = getenv("FAQCS_MI_STREAMING") && atoi(getenv("FAQCS_MI_STREAMING")) != 0;
-        if (!opt.in1.empty()) { if (!streaming && is_plain_regular_file(opt.in1) && is_plain_regular_file(opt.in2)) process_mapped(r, true); else process_paired(r); }
-        if (!opt.inu.empty()) { if (!streaming && is_plain_regular_file(opt.inu)) process_mapped(r, false); else process_unpaired(r); }
+        if (!opt.in1.empty()) { if (!streaming && is_plain_regular_file(opt.in1) && is_plain_regular_file(opt.in2)) process_mapped(r, true); else process_streamed(r, true); }
+        if (!opt.inu.empty()) { if (!streaming && is_plain_regular_file(opt.inu)) process_mapped(r, false); else process_streamed(r, false); }
         r.ensure_ctx();
         faqcs_layout L;
         faqcs_counters_layout(r.R, r.prm.n_adapters, &L);

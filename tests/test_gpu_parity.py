@@ -1588,7 +1588,7 @@ def test_native_cli_streaming_path_writes_what_came_before_a_device_error(mode, 
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
     assert r.returncode == 1, (r.returncode, r.stderr.decode()[-500:])
     assert b"Caught the error fastq.h:quality_score" in r.stderr
-    if mode == "unpaired":  # (process_unpaired's own gate / formatters / committer)
+    if mode == "unpaired":  # (process_streamed without a second file: one text, one committer)
         assert open(os.path.join(d, "QC.unpaired.trimmed.fastq"), "rb").read() == want[0]
         return
     got1, got2 = open(os.path.join(d, "QC.1.trimmed.fastq"), "rb").read(), open(os.path.join(d, "QC.2.trimmed.fastq"), "rb").read()
@@ -1672,9 +1672,10 @@ def test_native_cli_equals_the_reference_run_here_on_fresh_pairs(args, maxlen, t
     assert not bad, bad
 
 
-@pytest.mark.parametrize("args", [[], ["--discard", "--adapter"], ["-u"]], ids=["paired", "paired_discard_adapter", "unpaired"])
+@pytest.mark.parametrize("args", [[], ["--discard", "--adapter"], ["-u"], ["--out_ascii", "64", "--replace_to_N_q", "10", "--discard"], ["--qc_only"], ["-u", "--out_ascii", "64"]],
+                         ids=["paired", "paired_discard_adapter", "unpaired", "paired_edited_discard", "paired_qc_only", "unpaired_out_ascii64"])
 def test_native_cli_mapped_path_equals_streaming_path(args, tmp_path):
-    """faqcs_mi reads uncompressed regular files through the memory-mapped path (parallel index / parse / format, pwrite at
+    """faqcs_mi reads uncompressed regular files through the memory-mapped path (parallel index / parse / format, stores at
     offsets handed out in input order) and everything else through the streaming path (FAQCS_MI_STREAMING=1 forces it):
     same bytes in every output file on an input of several 32 768-record buffers with ragged lengths, a last buffer that is
     short, and records without a final newline."""
@@ -1698,8 +1699,8 @@ def test_native_cli_mapped_path_equals_streaming_path(args, tmp_path):
     outs = []
     for mode, env in (("mapped", {}), ("streaming", {"FAQCS_MI_STREAMING": "1"})):
         d = str(tmp_path / mode)
-        if args == ["-u"]:
-            cmd = [_CLI_BIN, "-u", p1, "-d", d, "--debug", "--discard"]
+        if args[:1] == ["-u"]:
+            cmd = [_CLI_BIN, "-u", p1, "-d", d, "--debug", "--discard"] + args[1:]
         else:
             cmd = [_CLI_BIN, "-1", p1, "-2", p2, "-d", d, "--debug"] + args
         r = subprocess.run(cmd, env=dict(os.environ, **env), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)

@@ -108,7 +108,7 @@ if os.environ.get("FAQCS_E2E_GZ"):
             r1 = resource.getrusage(resource.RUSAGE_CHILDREN)
             print("%s input%s, one process: %.3f s wall, %.1f s user, %.1f s system, %d minor faults (rc %d)"
                   % (tag, what, dt, r1.ru_utime - r0.ru_utime, r1.ru_stime - r0.ru_stime, r1.ru_minflt - r0.ru_minflt, r.returncode))
-if os.environ.get("FAQCS_E2E_GZ") and os.environ.get("FAQCS_E2E_UNPAIRED"):  # one file as unpaired input (process_unpaired's streaming path)
+if os.environ.get("FAQCS_E2E_GZ") and os.environ.get("FAQCS_E2E_UNPAIRED"):  # one file as unpaired input (process_streamed without a second file)
     for tag, gp in gz_sets.items():
         for rep in range(2):
             out = os.path.join(base, "out")

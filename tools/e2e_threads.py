@@ -1,5 +1,6 @@
-"""Diagnostic (not a test): faqcs_mi end to end on synthetic 2x150 FASTQ in /dev/shm for several parser / formatter / prefaulter thread
-counts, forked and in one process, best of two runs each.  python tools/e2e_threads.py [pairs]   -> profiles/r5*/e2e_threads.txt"""
+"""Diagnostic (not a test): faqcs_mi end to end on synthetic 2x150 FASTQ in /dev/shm for several parser / formatter thread counts,
+forked and in one process, best of two runs each.  python tools/e2e_threads.py [pairs]   -> profiles/r5*/e2e_threads.txt
+(The runs recorded there have a third column, the prefault helper threads of FAQCS_MI_PREFAULTERS: they lost and were removed.)"""
 import os
 import subprocess
 import sys
@@ -44,7 +45,7 @@ for mate in (1, 2):
             done += m
 cli = os.path.join(ROOT, "faqcs_amd", "faqcs_mi")
 print("host threads: %d; %d pairs 2x%d (%.1f GB in)" % (os.cpu_count(), n, L, 2 * os.path.getsize(paths[0]) / 1e9))
-for par, fmt, pre in ((16, 16, 0), (16, 16, 16), (40, 40, 0), (40, 40, 16), (24, 40, 16), (40, 64, 32), (0, 0, -1)):
+for par, fmt in ((16, 16), (40, 40), (24, 40), (40, 64), (0, 0)):
     for nofork in (0, 1):
         best, marks = None, ""
         for rep in range(2):
@@ -52,7 +53,7 @@ for par, fmt, pre in ((16, 16, 0), (16, 16, 16), (40, 40, 0), (40, 40, 16), (24,
             subprocess.run(["rm", "-rf", out])
             env = dict(os.environ, FAQCS_MI_TIMING="1")
             if par:
-                env.update(FAQCS_MI_PARSERS=str(par), FAQCS_MI_FORMATTERS=str(fmt), FAQCS_MI_PREFAULTERS=str(pre))
+                env.update(FAQCS_MI_PARSERS=str(par), FAQCS_MI_FORMATTERS=str(fmt))
             if nofork:
                 env["FAQCS_MI_NO_FORK"] = "1"
             t0 = time.perf_counter()
@@ -62,6 +63,6 @@ for par, fmt, pre in ((16, 16, 0), (16, 16, 16), (40, 40, 0), (40, 40, 16), (24,
             if r.returncode == 0 and (best is None or dt < best):
                 best = dt
                 marks = " | ".join(ln.strip() for ln in r.stderr.decode(errors="replace").splitlines() if "parsers:" in ln or "first pair" in ln or "outputs written" in ln)
-        label = "parsers %d formatters %d prefaulters %d" % (par, fmt, pre) if par else "defaults"
-        print("%-46s %s: %.3f s = %5.1f M reads/s   %s" % (label, "one process" if nofork else "forked     ", best or -1, 2 * n / (best or 1e9) / 1e6, marks[:260]))
+        label = "parsers %d formatters %d" % (par, fmt) if par else "defaults"
+        print("%-30s %s: %.3f s = %5.1f M reads/s   %s" % (label, "one process" if nofork else "forked     ", best or -1, 2 * n / (best or 1e9) / 1e6, marks[:260]))
 subprocess.run(["rm", "-rf", base])
