@@ -77,6 +77,25 @@ class RenderOut(C.Structure):
     _fields_ = [("text", C.c_void_p), ("capacity_bytes", C.c_uint64), ("rec_offset", C.c_void_p), ("rec_index", C.c_void_p), ("info", C.c_void_p)]
 
 
+# FAQCS_INFLATE_*: faqcs_inflate_info.error / faqcs_bgzf_index_info.error, the error of member n_members
+INFLATE_OK, INFLATE_E_HEADER, INFLATE_E_LENGTH, INFLATE_E_DATA, INFLATE_E_CRC, INFLATE_E_TRUNCATED = range(6)
+
+
+class BgzfIndexInfo(C.Structure):
+    """faqcs_bgzf_index_info: the whole members of a chunk of BGZF bytes and where the next chunk starts."""
+    _fields_ = [("consumed", C.c_uint64), ("n_members", C.c_uint32), ("overflow", C.c_uint32), ("error", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class InflateInfo(C.Structure):
+    """faqcs_inflate_info: what the text of the members needs (always), whether it fitted, and the first bad member."""
+    _fields_ = [("n_bytes", C.c_uint64), ("n_members", C.c_uint32), ("overflow", C.c_uint32), ("error", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class InflateOut(C.Structure):
+    """faqcs_inflate_out: the caller's output arrays (device pointers for faqcs_inflate_device, host pointers for faqcs_inflate_host)."""
+    _fields_ = [("text", C.c_void_p), ("capacity_bytes", C.c_uint64), ("member_text_offset", C.c_void_p), ("info", C.c_void_p)]
+
+
 # FAQCS_PARSE_*: faqcs_parse_info.error, the error of record n_reads
 PARSE_OK, PARSE_E_SEQUENCE, PARSE_E_PLUS, PARSE_E_PLUS_DELIM, PARSE_E_QUALITY, PARSE_E_LENGTH = range(6)
 
@@ -191,6 +210,11 @@ def load_library():
         "faqcs_render_device": (i32, [vp, C.POINTER(Batch), vp, vp, vp, vp, vp, vp, C.POINTER(RenderOut)]),
         "faqcs_render_host": (i32, [C.POINTER(Params), C.POINTER(Batch), vp, vp, vp, vp, vp, vp, C.POINTER(RenderOut)]),
         "faqcs_render_time_ms": (i32, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+        "faqcs_inflate_error_text": (C.c_char_p, [i32]),
+        "faqcs_bgzf_index_host": (i32, [vp, u64, i32, vp, u32, C.POINTER(BgzfIndexInfo)]),
+        "faqcs_inflate_device": (i32, [vp, vp, u64, vp, u32, C.POINTER(InflateOut)]),
+        "faqcs_inflate_host": (i32, [vp, u64, vp, u32, C.POINTER(InflateOut)]),
+        "faqcs_inflate_time_ms": (i32, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "faqcs_submit_async": (i32, [vp, C.POINTER(Batch), vp, C.POINTER(u64)]),
         "faqcs_wait": (i32, [vp, u64]),
         "faqcs_host_alloc": (vp, [C.c_size_t]),

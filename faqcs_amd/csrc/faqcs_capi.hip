@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "faqcs_dev.h"
+#include "faqcs_inflate.h"
 #include "faqcs_kmer.h"
 #include "faqcs_skm.h"
 
@@ -62,6 +63,10 @@ hipError_t faqcs_launch_render_scan(const faqcs_batch *b, const faqcs_read_resul
                                     const uint8_t *select, const uint32_t *order, const faqcs_render_out *out, void *scratch, hipStream_t st);
 hipError_t faqcs_launch_render_gather(const faqcs_batch *b, bool trimmed, const uint8_t *text, const faqcs_render_out *out, const void *scratch,
                                       int in_off, int out_off, uint32_t replace_q, int n_cu, hipStream_t st);
+
+size_t faqcs_inflate_scratch_bytes(uint32_t n_members);
+hipError_t faqcs_launch_inflate_scan(const uint8_t *comp, unsigned long long n_comp, const uint32_t *moff, uint32_t n, const faqcs_inflate_out *out, void *scratch, hipStream_t st);
+hipError_t faqcs_launch_inflate_decode(const uint8_t *comp, const uint32_t *moff, uint32_t n, const faqcs_inflate_out *out, void *scratch, int n_cu, hipStream_t st);
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string &msg) { g_err = msg; return code; }
@@ -149,6 +154,7 @@ struct faqcs_ctx {
     PackStage emit;   // the scan's tile sums and the 16-byte record of every emitted read | scan, gather
     PackStage parse;  // the line index, the record lengths and the two scans' tile sums | index + records, gather
     PackStage render; // the 32-byte descriptor and the text offset of every rendered record, the scan's tile sums | scan, gather
+    PackStage inflate; // the header fields, the position and the status of every member, the scan's tile sums | scan, decode
     // per-read composition records (trim kernel -> composition_histogram).  Two sets: the histogram kernels of
     // submission k run on the aux stream next to the trim kernel of submission k+1 (LDS-bound next to VALU-bound).
     struct RecSet { DevBuf<unsigned long long> pre, post; hipEvent_t trimmed = nullptr, folded = nullptr; bool used = false; };
@@ -533,7 +539,7 @@ extern "C" void faqcs_destroy(faqcs_ctx *c)
     for (auto &t : c->timings) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); (void)hipEventDestroy(t.p); (void)hipEventDestroy(t.k0); (void)hipEventDestroy(t.k1); }
     if (c->comm) comm_release(c->comm);
     if (c->comm_ev) (void)hipEventDestroy(c->comm_ev);
-    c->emit.release(); c->parse.release(); c->render.release();
+    c->emit.release(); c->parse.release(); c->render.release(); c->inflate.release();
     if (c->ins_a) (void)hipEventDestroy(c->ins_a);
     if (c->ins_b) (void)hipEventDestroy(c->ins_b);
     for (int k = 0; k < 2; ++k) { if (c->fwd_free[k]) (void)hipEventDestroy(c->fwd_free[k]); if (c->fwd_copied[k]) (void)hipEventDestroy(c->fwd_copied[k]); c->fwd_items[k].release(); }
@@ -1479,6 +1485,93 @@ extern "C" int faqcs_render_time_ms(faqcs_ctx *c, double *scan_ms, double *gathe
 {
     if (!c || !scan_ms || !gather_ms) return fail(FAQCS_E_INVAL, "null argument");
     return c->render.times(c, "faqcs_render_time_ms: no rendering on this context yet", scan_ms, gather_ms);
+}
+
+static const char *const INFLATE_TEXT[] = {"", "bgzf: not a BGZF member header", "bgzf: the decoded length differs from ISIZE",
+                                           "bgzf: invalid deflate data", "bgzf: the CRC-32 differs from the trailer", "bgzf: the last member is incomplete"};
+extern "C" const char *faqcs_inflate_error_text(int code) { return code >= 0 && code <= FAQCS_INFLATE_E_TRUNCATED ? INFLATE_TEXT[code] : nullptr; }
+
+extern "C" int faqcs_bgzf_index_host(const uint8_t *comp, uint64_t n_comp, int final, uint32_t *member_offset, uint32_t capacity_members, faqcs_bgzf_index_info *info)
+{
+    if (!info || !member_offset || (!comp && n_comp)) return fail(FAQCS_E_INVAL, "faqcs_bgzf_index_host: null input, offsets or info");
+    if (n_comp >= (1ull << 32)) return fail(FAQCS_E_INVAL, "faqcs_bgzf_index_host: 2^32 bytes or more must be cut into chunks (final = 0, consumed)");
+    faqcs_inflate::IndexInfo ii{};
+    faqcs_inflate::bgzf_index(comp, n_comp, final, member_offset, capacity_members, ii);
+    info->consumed = ii.consumed; info->n_members = ii.n_members; info->overflow = ii.overflow; info->error = ii.error; info->reserved = 0;
+    return 0;
+}
+
+static int inflate_check_args(const char *who, const uint8_t *comp, uint64_t n_comp, const uint32_t *member_offset, uint32_t n_members, const faqcs_inflate_out *out)
+{
+    const std::string w(who);
+    if (!out || !out->text || !out->info) return fail(FAQCS_E_INVAL, w + ": null output, text or info");
+    if (n_members && (!comp || !member_offset)) return fail(FAQCS_E_INVAL, w + ": null input or member offsets");
+    if ((uintptr_t)out->text & 15u) return fail(FAQCS_E_INVAL, w + ": the output text must be 16-byte aligned");
+    if (n_comp >= (1ull << 32)) return fail(FAQCS_E_INVAL, w + ": 2^32 compressed bytes or more must be cut into chunks");
+    if (n_members > n_comp / faqcs_inflate::MIN_MEMBER) return fail(FAQCS_E_INVAL, w + ": more members than the input can hold");
+    return 0;
+}
+
+extern "C" int faqcs_inflate_device(faqcs_ctx *c, const uint8_t *d_comp, uint64_t n_comp, const uint32_t *d_member_offset, uint32_t n_members, const faqcs_inflate_out *out)
+{
+    if (!c) return fail(FAQCS_E_INVAL, "null ctx");
+    if (int rc = inflate_check_args("faqcs_inflate_device", d_comp, n_comp, d_member_offset, n_members, out)) return rc;
+    if (int rc = c->inflate.begin(c, faqcs_inflate_scratch_bytes(n_members))) return rc;
+    HIPCHK(faqcs_launch_inflate_scan(d_comp, n_comp, d_member_offset, n_members, out, c->inflate.scratch.p, c->compute));
+    if (int rc = c->inflate.mark(1)) return rc;
+    HIPCHK(faqcs_launch_inflate_decode(d_comp, d_member_offset, n_members, out, c->inflate.scratch.p, c->n_cu, c->compute));
+    return c->inflate.mark(2);
+}
+
+extern "C" int faqcs_inflate_time_ms(faqcs_ctx *c, double *scan_ms, double *decode_ms)
+{
+    if (!c || !scan_ms || !decode_ms) return fail(FAQCS_E_INVAL, "null argument");
+    return c->inflate.times(c, "faqcs_inflate_time_ms: no inflate on this context yet", scan_ms, decode_ms);
+}
+
+// The host statement of the inflate rules (include/faqcs_mi.h at faqcs_inflate_device): the scan over every member's header, then -- when
+// the total fits -- the members in input order up to the first bad one, each decoded into a buffer of its own first, so that exactly
+// text[0 .. n_bytes) is written.
+extern "C" int faqcs_inflate_host(const uint8_t *comp, uint64_t n_comp, const uint32_t *member_offset, uint32_t n_members, const faqcs_inflate_out *out)
+{
+    namespace inf = faqcs_inflate;
+    if (int rc = inflate_check_args("faqcs_inflate_host", comp, n_comp, member_offset, n_members, out)) return rc;
+    faqcs_inflate_info info{};
+    auto header = [&](uint32_t k, inf::Member &m) -> int {
+        const uint32_t a = member_offset[k], e = member_offset[k + 1];
+        m = inf::Member{0, 0, 0, 0};
+        return (e > a && e <= n_comp) ? inf::parse_member(comp + a, e - a, m) : (int)inf::ST_E_HEADER;
+    };
+    uint64_t total = 0;
+    for (uint32_t k = 0; k < n_members; ++k) {
+        inf::Member m;
+        if (!header(k, m)) total += m.isize;
+    }
+    info.n_bytes = total; info.n_members = n_members;
+    info.overflow = (total > out->capacity_bytes || total >= (1ull << 32)) ? 1u : 0u;
+    if (!info.overflow) {
+        std::vector<uint8_t> one(inf::MAX_ISIZE);
+        std::unique_ptr<inf::Tables> T(new inf::Tables);
+        inf::HostSink S{one.data()};
+        inf::crc_init(*T, S);
+        uint64_t pos = 0;
+        bool bad = false;
+        if (out->member_text_offset) out->member_text_offset[0] = 0;
+        for (uint32_t k = 0; k < n_members; ++k) {
+            inf::Member m;
+            int st = header(k, m);
+            const uint32_t isz = st ? 0u : m.isize;
+            if (!bad) {
+                if (!st) st = inf::inflate_member_host(comp + member_offset[k], member_offset[k + 1] - member_offset[k], *T, one.data(), m);
+                if (st) { bad = true; info.n_bytes = pos; info.n_members = k; info.error = st; }
+                else if (m.isize) memcpy(out->text + pos, one.data(), m.isize);
+            }
+            pos += isz;
+            if (out->member_text_offset) out->member_text_offset[k + 1] = (uint32_t)pos;
+        }
+    }
+    *out->info = info;
+    return 0;
 }
 
 // The host statement of the render rules (include/faqcs_mi.h at faqcs_render_device).  Two passes over the candidates: what the records need,

@@ -1,0 +1,205 @@
+// faqcs_inflate_kernel.hip -- faqcs_inflate_device: BGZF members in HBM to the FASTQ text faqcs_parse_device takes (include/faqcs_mi.h,
+// DESIGN.md section 4.8).  The decoder itself is faqcs_inflate.h, the text the host statement and the sanitizer build compile too; this
+// file holds the wave that executes it and the kernels around it:
+//
+//   inflate_scan      one thread per member: header and trailer, the header rules, ISIZE; block scan of ISIZE, a tile sum per block
+//   scan_tile_sums    (faqcs_pack_common.h) one block: tile prefixes, the total, the overflow decision
+//   inflate_apply     one thread per member: its output position
+//   inflate_decode    ONE WAVE PER MEMBER: blocks of one wave claim members by a strided loop; tables in LDS, built by the lanes over the
+//                     symbols; the bit buffer is the same in every lane (scalar registers), a table look-up is one LDS address; literals
+//                     collect one per lane and leave as one store per 64 bytes; a match is one load and one store per lane; the window is
+//                     the output buffer itself; the CRC runs in the tail, a slice per lane
+//   inflate_finish    one block: the first bad member in input order completes info
+// No global atomic anywhere: every member's wave writes its own status word.
+#include "faqcs_inflate.h"
+#include "faqcs_pack_common.h"
+
+using namespace faqcs_pack;
+namespace inf = faqcs_inflate;
+
+namespace {
+
+constexpr uint32_t SCAN_TILE = 256;    // members of an inflate_scan block
+constexpr uint32_t FINISH_THREADS = 1024;
+constexpr uint32_t DECODE_BLOCKS_PER_CU = 24; // 5.4 KB of LDS each
+
+// the leading 16 bytes of faqcs_inflate_info under the field names scan_tile_sums asserts
+struct ScanHead { unsigned long long n_bytes; uint32_t n_reads, overflow; };
+static_assert(offsetof(faqcs_inflate_info, n_bytes) == 0 && offsetof(faqcs_inflate_info, n_members) == 8 && offsetof(faqcs_inflate_info, overflow) == 12 &&
+              offsetof(faqcs_inflate_info, error) == 16 && sizeof(faqcs_inflate_info) == 24, "faqcs_inflate_info leads with {n_bytes, n_members, overflow}, error behind them");
+
+struct Scratch {
+    TileSum *tiles; TilePrefix *prefix; uint4 *hdr; uint32_t *pos, *status;
+    size_t bytes;
+};
+inline Scratch carve(void *base, uint32_t n)
+{
+    const size_t nt = ((size_t)n + SCAN_TILE - 1) / SCAN_TILE;
+    auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    Scratch s;
+    uint8_t *p = (uint8_t *)base;
+    s.tiles = (TileSum *)p; p += up((nt + 1) * sizeof(TileSum));
+    s.prefix = (TilePrefix *)p; p += up((nt + 1) * sizeof(TilePrefix));
+    s.hdr = (uint4 *)p; p += up(((size_t)n + 1) * sizeof(uint4));
+    s.pos = (uint32_t *)p; p += up(((size_t)n + 1) * sizeof(uint32_t));
+    s.status = (uint32_t *)p; p += up(((size_t)n + 1) * sizeof(uint32_t));
+    s.bytes = (size_t)(p - (uint8_t *)base);
+    return s;
+}
+
+__global__ __launch_bounds__(SCAN_TILE) void inflate_scan(const uint8_t *__restrict__ comp, const unsigned long long n_comp, const uint32_t *__restrict__ moff, const uint32_t n,
+                                                          uint4 *__restrict__ hdr, uint32_t *__restrict__ status, uint32_t *__restrict__ pos, TileSum *__restrict__ tiles)
+{
+    __shared__ uint32_t s_a[SCAN_TILE / 64];
+    const uint32_t first = blockIdx.x * SCAN_TILE, i = first + threadIdx.x;
+    uint32_t isz = 0;
+    if (i < n) {
+        const uint32_t a = moff[i], e = moff[i + 1];
+        inf::Member m{0, 0, 0, 0};
+        int st = inf::ST_E_HEADER;
+        if (e > a && e <= n_comp) st = inf::parse_member(comp + a, e - a, m); // (reads inside comp[a .. e) only)
+        hdr[i] = make_uint4(m.data_begin, m.data_end, m.crc, m.isize);
+        status[i] = (uint32_t)st;
+        isz = st ? 0u : m.isize;
+    }
+    uint32_t pre, tot;
+    block_excl_scan<uint32_t, (int)SCAN_TILE>(isz, s_a, pre, tot); // (256 x 65 536 = 2^24)
+    if (i < n) pos[i + 1] = pre + isz;
+    if (threadIdx.x == 0) tiles[blockIdx.x] = TileSum{tot, n - first < SCAN_TILE ? n - first : SCAN_TILE, 0};
+}
+
+__global__ __launch_bounds__(SCAN_TILE) void inflate_apply(const TilePrefix *__restrict__ prefix, const uint32_t n, uint32_t *__restrict__ pos,
+                                                           uint32_t *__restrict__ member_text_offset, const faqcs_inflate_info *__restrict__ info)
+{
+    const uint32_t i = blockIdx.x * SCAN_TILE + threadIdx.x;
+    if (i >= n || info->overflow) return;
+    const uint32_t p = pos[i + 1] + (uint32_t)prefix[blockIdx.x].bytes;
+    pos[i + 1] = p;
+    if (member_text_offset) member_text_offset[i + 1] = p;
+}
+
+// One wave as the decoder's Sink.  Literals wait one per lane -- output byte o in lane o mod 64 -- and leave together when the 64-byte
+// window is full or a copy needs them in memory.  A copy reads bytes that are all in memory before it starts (byte i of a match comes from
+// o - dist + i mod dist < o), so it is one load and one store per lane and 64 bytes, with no wait inside it; the wave reads back its own
+// stores behind a fence of wavefront scope.
+struct WaveSink {
+    uint8_t *out;
+    uint32_t l, lo, hi, mine;
+    __device__ __forceinline__ uint32_t lane() const { return l; }
+    __device__ __forceinline__ uint32_t lanes() const { return 64; }
+    __device__ __forceinline__ void sync() { __syncthreads(); } // (the block is this wave)
+    __device__ __forceinline__ uint32_t uni(uint32_t v) const { return uniu(v); }
+    __device__ __forceinline__ void flush()
+    {
+        if (hi > lo) {
+            const uint32_t a = (lo & ~63u) | l;
+            if (a >= lo && a < hi) out[a] = (uint8_t)mine;
+            lo = hi;
+        }
+    }
+    __device__ __forceinline__ void lit(uint32_t o, uint32_t v)
+    {
+        if (hi == lo) lo = hi = o;
+        if ((o & 63u) == l) mine = v;
+        hi = o + 1;
+        if ((hi & 63u) == 0) flush();
+    }
+    __device__ __forceinline__ void own_stores_visible() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); }
+    __device__ __forceinline__ void match(uint32_t o, uint32_t len, uint32_t dist)
+    {
+        flush();
+        own_stores_visible();
+        const uint8_t *src = out + o - dist;
+        uint8_t v[5];
+#pragma unroll
+        for (uint32_t k = 0; k < 5; ++k) { // (len <= 258)
+            const uint32_t i = l + 64 * k;
+            if (i < len) v[k] = src[dist >= len ? i : i % dist];
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < 5; ++k) {
+            const uint32_t i = l + 64 * k;
+            if (i < len) out[o + i] = v[k];
+        }
+    }
+    __device__ __forceinline__ void stored(uint32_t o, const uint8_t *src, uint32_t len)
+    {
+        flush();
+        for (uint32_t i = l; i < len; i += 64) out[o + i] = src[i];
+    }
+};
+
+__global__ __launch_bounds__(64) void inflate_decode(const uint8_t *__restrict__ comp, const uint32_t *__restrict__ moff, const uint32_t n, const uint4 *__restrict__ hdr,
+                                                     const uint32_t *__restrict__ pos, uint32_t *__restrict__ status, uint8_t *text, const faqcs_inflate_info *__restrict__ info)
+{
+    __shared__ inf::Tables T;
+    if (info->overflow) return;
+    WaveSink S;
+    S.l = threadIdx.x; S.out = text; S.lo = S.hi = 0; S.mine = 0;
+    inf::crc_init(T, S);
+    for (uint32_t m = blockIdx.x; m < n; m += gridDim.x) {
+        if (uniu(status[m])) continue; // the scan refused its header
+        const uint4 h = hdr[m];
+        const uint32_t begin = uniu(h.x), end = uniu(h.y), crc_want = uniu(h.z), isize = uniu(h.w);
+        S.out = text + uniu(pos[m]); // [pos, pos + isize) lies inside the scanned total, which fits the capacity
+        S.lo = S.hi = 0;
+        int st = inf::inflate_member(comp + uniu(moff[m]), begin, end, isize, T, S);
+        if (!st) {
+            S.own_stores_visible();
+            uint32_t c = inf::crc_slice(T, S.out, isize, S.l);
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) c ^= (uint32_t)__shfl_xor((int)c, d);
+            if (uniu(c) != crc_want) st = inf::ST_E_CRC;
+        }
+        if (st && S.l == 0) status[m] = (uint32_t)st;
+    }
+}
+
+__global__ __launch_bounds__(FINISH_THREADS) void inflate_finish(const uint32_t *__restrict__ status, const uint32_t *__restrict__ pos, const uint32_t n, faqcs_inflate_info *__restrict__ info)
+{
+    __shared__ uint32_t s_min[FINISH_THREADS / 64];
+    uint32_t best = 0xffffffffu;
+    if (!info->overflow)
+        for (uint32_t i = threadIdx.x; i < n; i += FINISH_THREADS)
+            if (status[i]) { best = i; break; }
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) best = umin_(best, (uint32_t)__shfl_xor((int)best, d));
+    if ((threadIdx.x & 63u) == 0) s_min[threadIdx.x >> 6] = best;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (uint32_t w = 0; w < FINISH_THREADS / 64; ++w) best = umin_(best, s_min[w]);
+        int32_t err = inf::ST_OK;
+        if (best != 0xffffffffu) {
+            info->n_bytes = pos[best];
+            info->n_members = best;
+            err = (int32_t)status[best];
+        }
+        info->error = err;
+        info->reserved = 0;
+    }
+}
+
+} // namespace
+
+size_t faqcs_inflate_scratch_bytes(uint32_t n_members) { return carve(nullptr, n_members).bytes; }
+
+// the scan: every member's header, its position, the total and the overflow decision
+hipError_t faqcs_launch_inflate_scan(const uint8_t *comp, unsigned long long n_comp, const uint32_t *moff, uint32_t n, const faqcs_inflate_out *out, void *scratch, hipStream_t st)
+{
+    const Scratch s = carve(scratch, n);
+    const uint32_t nt = (n + SCAN_TILE - 1) / SCAN_TILE;
+    if (n) hipLaunchKernelGGL(inflate_scan, dim3(nt), dim3(SCAN_TILE), 0, st, comp, n_comp, moff, n, s.hdr, s.status, s.pos, s.tiles);
+    hipLaunchKernelGGL(scan_tile_sums<ScanHead>, dim3(1), dim3(SCAN_THREADS), 0, st, s.tiles, nt, s.prefix, (unsigned long long)out->capacity_bytes,
+                       reinterpret_cast<ScanHead *>(out->info), s.pos, out->member_text_offset);
+    if (n) hipLaunchKernelGGL(inflate_apply, dim3(nt), dim3(SCAN_TILE), 0, st, s.prefix, n, s.pos, out->member_text_offset, out->info);
+    return hipGetLastError();
+}
+
+hipError_t faqcs_launch_inflate_decode(const uint8_t *comp, const uint32_t *moff, uint32_t n, const faqcs_inflate_out *out, void *scratch, int n_cu, hipStream_t st)
+{
+    const Scratch s = carve(scratch, n);
+    const uint32_t cap = (uint32_t)(n_cu > 0 ? n_cu : 256) * DECODE_BLOCKS_PER_CU;
+    if (n) hipLaunchKernelGGL(inflate_decode, dim3(n < cap ? n : cap), dim3(64), 0, st, comp, moff, n, s.hdr, s.pos, s.status, out->text, out->info);
+    hipLaunchKernelGGL(inflate_finish, dim3(1), dim3(FINISH_THREADS), 0, st, s.status, s.pos, n, out->info);
+    return hipGetLastError();
+}

@@ -1,5 +1,5 @@
 """Torch-facing helpers of the device seam: inputs and outputs are torch tensors that live on the GPU; the work is the
-library's HIP kernels (faqcs_emit_device, faqcs_render_device), never torch ops."""
+library's HIP kernels (faqcs_emit_device, faqcs_render_device, faqcs_inflate_device), never torch ops."""
 import ctypes as C
 
 from . import _capi as capi
@@ -79,3 +79,46 @@ def rendered_fastq(engine, text, def_pos, def_len, seq, qual, offset, results=No
     if overflow:
         raise FaqcsError(capi.E_INVAL, "faqcs_render_device: the text needs %d bytes, the output holds %d" % (n_bytes, cap))
     return o_text[shift:shift + n_bytes], o_off[:n_rec + 1]
+
+
+def inflated_text(engine, comp, member_offset=None, capacity=None):
+    """The text of BGZF-compressed input, inflated on the device (faqcs_inflate_device).
+
+    comp: uint8 CUDA tensor, the compressed bytes (whole members; any alignment); member_offset: int32 / uint32 tensor or numpy array
+    [n_members + 1], or None: the members are found on the host (faqcs_bgzf_index_host), which copies `comp` there -- a caller that
+    uploads a file has those bytes on the host already and passes the offsets.  capacity: bytes of text to make room for (default
+    65 536 per member, which no member exceeds).  Returns (text, member_text_offset): uint8 [n_bytes] -- a view that starts 16-byte
+    aligned, 64 bytes into its storage, with 64 spare bytes behind: a valid d_text for faqcs_parse_device() --, int32 [n_members + 1]
+    (bit pattern of uint32).  A bad member raises FaqcsError with faqcs_inflate_error_text and the member's index."""
+    import numpy as np
+    import torch
+
+    dev = comp.device
+    if member_offset is None:
+        from .engine import bgzf_index_host
+        moff, consumed, err = bgzf_index_host(comp.cpu().numpy(), True, engine.lib)
+        if err:
+            raise FaqcsError(capi.E_INVAL, "member %d: %s" % (len(moff) - 1, engine.lib.faqcs_inflate_error_text(err).decode()))
+        member_offset = moff
+    if isinstance(member_offset, np.ndarray):
+        member_offset = torch.from_numpy(member_offset.astype(np.int64).astype(np.uint32).view(np.int32)).to(dev)
+    member_offset = member_offset.contiguous()
+    n = int(member_offset.numel()) - 1
+    cap = 65536 * n if capacity is None else int(capacity)
+    front = 64
+    o_text = torch.empty(front + cap + capi.ARENA_PAD_AFTER + 16, dtype=torch.uint8, device=dev)
+    o_off = torch.empty(n + 1, dtype=torch.int32, device=dev)
+    info = torch.zeros(3, dtype=torch.int64, device=dev)
+    shift = (-(o_text.data_ptr() + front)) % 16
+    out = capi.InflateOut(o_text.data_ptr() + front + shift, cap, o_off.data_ptr(), info.data_ptr())
+    torch.cuda.current_stream(dev).synchronize()  # the library's compute stream is its own: the inputs must be complete
+    engine.inflate_device(comp.data_ptr(), int(comp.numel()), member_offset.data_ptr(), n, out)
+    engine.sync()
+    h = info.cpu().numpy()
+    n_bytes, n_mem, overflow, error = int(h[0]), int(h[1]) & 0xFFFFFFFF, int(h[1]) >> 32, int(h[2]) & 0xFFFFFFFF
+    if overflow:
+        raise FaqcsError(capi.E_INVAL, "faqcs_inflate_device: the text needs %d bytes, the output holds %d" % (n_bytes, cap))
+    if error:
+        raise FaqcsError(capi.E_INVAL, "member %d: %s" % (n_mem, engine.lib.faqcs_inflate_error_text(error).decode()))
+    a = front + shift
+    return o_text[a:a + n_bytes], o_off[:n_mem + 1]

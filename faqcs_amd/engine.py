@@ -26,6 +26,19 @@ def _check(lib, rc):
         raise FaqcsError(rc, msg)
 
 
+def bgzf_index_host(comp, final=True, lib=None):
+    """faqcs_bgzf_index_host (host only, no GPU): the BGZF members of `comp` (bytes or a uint8 array), walked from byte 0.
+    Returns (member_offset uint32 [n_members + 1], consumed, error): member k is comp[member_offset[k] : member_offset[k + 1]], `consumed`
+    is where the next chunk starts (final = False leaves an incomplete last member to the caller), error is a capi.INFLATE_* code."""
+    lib = lib or capi.load_library()
+    buf = np.frombuffer(comp, dtype=np.uint8) if isinstance(comp, (bytes, bytearray, memoryview)) else np.ascontiguousarray(comp, dtype=np.uint8)
+    cap = len(buf) // 26 + 1
+    off = np.zeros(cap + 1, dtype=np.uint32)
+    info = capi.BgzfIndexInfo()
+    _check(lib, lib.faqcs_bgzf_index_host(buf.ctypes.data if len(buf) else None, len(buf), 1 if final else 0, off.ctypes.data, cap, C.byref(info)))
+    return off[:info.n_members + 1].copy(), int(info.consumed), int(info.error)
+
+
 class HipEngine:
     name = "hip"
 
@@ -91,6 +104,22 @@ class HipEngine:
         a, g = C.c_double(), C.c_double()
         _check(self.lib, self.lib.faqcs_render_time_ms(self.ctx, C.byref(a), C.byref(g)))
         return a.value, g.value
+
+    def inflate_device(self, d_comp, n_comp, d_member_offset, n_members, out):
+        """faqcs_inflate_device: BGZF members in device memory (d_comp: device address, any alignment; d_member_offset: device uint32
+        [n_members + 1], as bgzf_index_host() found them) -> their text in the arrays of `out` (a capi.InflateOut of device pointers).
+        Enqueued; sync() waits."""
+        _check(self.lib, self.lib.faqcs_inflate_device(self.ctx, d_comp, int(n_comp), d_member_offset, int(n_members), C.byref(out)))
+
+    def inflate_time_ms(self):
+        """(scan ms, decode ms) of the last inflate_device() on this engine (HIP events on the compute stream); waits for it."""
+        a, g = C.c_double(), C.c_double()
+        _check(self.lib, self.lib.faqcs_inflate_time_ms(self.ctx, C.byref(a), C.byref(g)))
+        return a.value, g.value
+
+    def bgzf_index_host(self, comp, final=True):
+        """bgzf_index_host() of this module on the engine's library."""
+        return bgzf_index_host(comp, final, self.lib)
 
     def set_quality(self, q):
         _check(self.lib, self.lib.faqcs_set_quality(self.ctx, int(q)))

@@ -34,7 +34,7 @@ extern "C" {
  * Round 6 adds faqcs_kmer_finish_pass, and faqcs_sync() no longer counts the k-mers that wait in the open group (see below).
  * faqcs_emit_device (the trimmed, edited reads packed on the device) is a new entry point with structures of its own, and so are
  * faqcs_parse_device / faqcs_parse_host (FASTQ text to a packed batch) and faqcs_render_device / faqcs_render_host (the FASTQ text of the
- * output files). */
+ * output files), and faqcs_inflate_device / faqcs_inflate_host / faqcs_bgzf_index_host (BGZF members to that text). */
 #define FAQCS_ABI_VERSION 2
 
 /* FilterStat enum order, FaQCs.h:46-75 */
@@ -353,6 +353,77 @@ int  faqcs_render_host(const faqcs_params *p, const faqcs_batch *batch, const fa
                        const uint8_t *text, const uint32_t *def_pos, const uint32_t *def_len,
                        const uint8_t *select, const uint32_t *order, const faqcs_render_out *out);
 
+/* The step in front of the device seam: compressed input.  BGZF (bgzip) members in device memory -> the FASTQ text faqcs_parse_device()
+ * takes.  Ordinary single-stream gzip is not taken: it has no member boundaries (the command line's faqcs_pargz.h handles it on the host).
+ * A MEMBER:
+ *   - a gzip member whose header has ID1 ID2 CM = 1f 8b 08 and FLG.FEXTRA set, and whose extra field holds a 'B' 'C' subfield of length 2:
+ *     BSIZE, the member's total size - 1.  The acceptance rule is that of the command line's reader (BgzfReader::member_size): subfields in
+ *     front of BC are skipped, a member is at least 26 bytes.  FNAME, FCOMMENT and FHCRC are skipped as RFC 1952 defines them (FHCRC is not
+ *     verified); a reserved FLG bit is refused.
+ *   - behind the header one deflate stream (RFC 1951): stored, fixed and dynamic blocks.  Code sets are accepted as zlib accepts them (an
+ *     over-subscribed set is invalid; an incomplete one too, except a set without any code and -- not for the code-length code -- a single
+ *     code of one bit).  The stream ends in the byte in front of the trailer.
+ *   - the trailer: CRC-32 of the text and ISIZE, its length.  ISIZE <= 65 536.
+ *   - there is no dictionary: a back-reference that reaches in front of the member's own output is invalid.
+ * faqcs_bgzf_index_host: where the members are.  Plain host C++, no HIP call: walks the BSIZE chain of comp[0 .. n_comp) from byte 0 and
+ * writes member_offset[0 .. n_members] (capacity_members + 1 entries; member k is comp[member_offset[k] .. member_offset[k + 1])).
+ *   final = 0   a member whose bytes are not all inside the chunk is left to the caller (info->consumed is where the next chunk starts), no error
+ *   final = 1   an incomplete last member is FAQCS_INFLATE_E_TRUNCATED of member n_members
+ *   Bytes behind the last member that do not start a gzip header (1f 8b) end the data without an error, as they do for zlib's gzread
+ *   (DESIGN.md section 8): consumed = n_comp.  A gzip header that is not a BGZF member's is FAQCS_INFLATE_E_HEADER of member n_members, and
+ *   consumed is where it starts.  n_members > capacity_members: overflow = 1, info is complete and nothing else is written.
+ *   n_comp >= 2^32 or a null pointer is FAQCS_E_INVAL.  There is no device-side index: the chain is a serial pointer chase -- each header
+ *   says where the next one is -- that the host does in microseconds on bytes it has just read and is about to upload.
+ * faqcs_inflate_device: every pointer but ctx and out is a DEVICE pointer, out->info included.  Enqueued on the context's compute stream,
+ * returns at once; faqcs_sync() waits.  No alignment is asked of d_comp; member k is d_comp[d_member_offset[k] .. d_member_offset[k + 1]).
+ *   before decoding   every member's header and trailer are checked and the ISIZE of the members give each its position in the text and the
+ *                     total (a member whose header is refused counts 0).  total > capacity_bytes or total >= 2^32: overflow = 1, n_bytes and
+ *                     n_members are the totals, error = 0 and NOTHING but info is written: no truncation, ever.  A header that breaks the
+ *                     rules above (or offsets that are not increasing inside n_comp) is E_HEADER of that member, ISIZE > 65 536 E_LENGTH.
+ *   after decoding    a decoded length that differs from ISIZE is E_LENGTH; an invalid code or code set, block type 3, a stored block with
+ *                     LEN != ~NLEN, a distance in front of the member, input that runs out or is left over is E_DATA; a CRC that differs
+ *                     from the trailer is E_CRC.
+ *   Errors are sequential, as in the parse: the first bad member in input order decides, info->n_members is its index, info->n_bytes the
+ *   text of the members in front of it, and that text is delivered byte-exact (what lies behind it in `text` is unspecified).  Without an
+ *   error n_members and n_bytes are the totals.  The kernels touch only text[0 .. scanned total rounded up to 16), member_text_offset
+ *   [0 .. n_members] (all of them, error or not) and info; a member's decoder never writes outside its own [position, position + ISIZE),
+ *   whatever the compressed bytes say.  n_members == 0 yields zeros.  With FAQCS_ARENA_PAD_BEFORE readable bytes left in front of text and
+ *   FAQCS_ARENA_PAD_AFTER behind text + capacity_bytes by the caller, (text, n_bytes) is a valid d_text for faqcs_parse_device().
+ *   FAQCS_E_INVAL: n_comp >= 2^32, more members than n_comp / 26, a null ctx / out / out->text / out->info, a null d_comp or d_member_offset
+ *   with members, out->text not 16-byte aligned.  Scratch (24 bytes per member: header fields, position, status) is the library's: grown on
+ *   demand, freed by faqcs_destroy().
+ * faqcs_inflate_host is the same call with HOST pointers: the host statement of these rules, single-threaded, no HIP call and no zlib,
+ * built from the same decoder text as the kernel (csrc/faqcs_inflate.h).  It writes exactly text[0 .. n_bytes). */
+enum { FAQCS_INFLATE_OK = 0, FAQCS_INFLATE_E_HEADER, FAQCS_INFLATE_E_LENGTH, FAQCS_INFLATE_E_DATA, FAQCS_INFLATE_E_CRC, FAQCS_INFLATE_E_TRUNCATED };
+const char *faqcs_inflate_error_text(int code);   /* "" for FAQCS_INFLATE_OK, NULL for no code */
+
+typedef struct faqcs_bgzf_index_info {
+    uint64_t consumed;     /* compressed bytes covered by the indexed members: the next chunk starts here */
+    uint32_t n_members;    /* whole members found (== index of the bad member when error != 0) */
+    uint32_t overflow;     /* 1: n_members > capacity_members */
+    int32_t  error;        /* FAQCS_INFLATE_E_HEADER / _E_TRUNCATED of member n_members */
+    uint32_t reserved;
+} faqcs_bgzf_index_info;
+int  faqcs_bgzf_index_host(const uint8_t *comp, uint64_t n_comp, int final, uint32_t *member_offset, uint32_t capacity_members,
+                           faqcs_bgzf_index_info *info);
+
+typedef struct faqcs_inflate_info {
+    uint64_t n_bytes;      /* text bytes of the members in front of the first bad one (all of them when error == 0) */
+    uint32_t n_members;    /* members delivered (== index of the bad member when error != 0) */
+    uint32_t overflow;     /* 1: the scanned total > capacity_bytes or >= 2^32 */
+    int32_t  error;        /* FAQCS_INFLATE_* of member n_members */
+    uint32_t reserved;     /* 0 */
+} faqcs_inflate_info;
+typedef struct faqcs_inflate_out {
+    uint8_t  *text;                /* 16-byte aligned; capacity_bytes (+ FAQCS_ARENA_PAD_AFTER for faqcs_parse_device) */
+    uint64_t  capacity_bytes;
+    uint32_t *member_text_offset;  /* OPTIONAL, n_members + 1: [0] = 0, [k + 1] = end of member k's text */
+    faqcs_inflate_info *info;
+} faqcs_inflate_out;
+int  faqcs_inflate_device(faqcs_ctx *ctx, const uint8_t *d_comp, uint64_t n_comp, const uint32_t *d_member_offset, uint32_t n_members,
+                          const faqcs_inflate_out *out);
+int  faqcs_inflate_host(const uint8_t *comp, uint64_t n_comp, const uint32_t *member_offset, uint32_t n_members, const faqcs_inflate_out *out);
+
 /* Pipelined form of faqcs_submit(): returns a ticket; faqcs_wait(ticket) blocks until THAT batch's results have
  * landed in `results` (later batches may still be in flight: two input staging slots let the H2D copy of batch
  * k+1 overlap the kernels of batch k).  Host arenas / result arrays obtained from faqcs_host_alloc() are pinned,
@@ -485,6 +556,8 @@ int  faqcs_emit_time_ms(faqcs_ctx *ctx, double *scan_ms, double *gather_ms);
 int  faqcs_parse_time_ms(faqcs_ctx *ctx, double *index_ms, double *gather_ms);
 /* the same for the LAST faqcs_render_device() on the context: the scan (scan_ms), the gather (gather_ms) */
 int  faqcs_render_time_ms(faqcs_ctx *ctx, double *scan_ms, double *gather_ms);
+/* the same for the LAST faqcs_inflate_device() on the context: the scan of the headers (scan_ms), the decode with its CRC and the status (decode_ms) */
+int  faqcs_inflate_time_ms(faqcs_ctx *ctx, double *scan_ms, double *decode_ms);
 /* diagnostic builds only: section clocks accumulated by the trim kernel (16 words; read and cleared) */
 int  faqcs_debug_words(faqcs_ctx *ctx, uint64_t *out, uint32_t n);
 /* average duration (ms) of the dominant kernel over the launches since the last call, measured with
