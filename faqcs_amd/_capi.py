@@ -96,6 +96,16 @@ class InflateOut(C.Structure):
     _fields_ = [("text", C.c_void_p), ("capacity_bytes", C.c_uint64), ("member_text_offset", C.c_void_p), ("info", C.c_void_p)]
 
 
+class DeflateInfo(C.Structure):
+    """faqcs_deflate_info: what the members need (always), whether they fitted, and how many of them hold a stored block."""
+    _fields_ = [("n_bytes", C.c_uint64), ("n_members", C.c_uint32), ("overflow", C.c_uint32), ("n_stored", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class DeflateOut(C.Structure):
+    """faqcs_deflate_out: the caller's output arrays (device pointers for faqcs_deflate_device, host pointers for faqcs_deflate_host)."""
+    _fields_ = [("comp", C.c_void_p), ("capacity_bytes", C.c_uint64), ("member_offset", C.c_void_p), ("info", C.c_void_p)]
+
+
 # FAQCS_PARSE_*: faqcs_parse_info.error, the error of record n_reads
 PARSE_OK, PARSE_E_SEQUENCE, PARSE_E_PLUS, PARSE_E_PLUS_DELIM, PARSE_E_QUALITY, PARSE_E_LENGTH = range(6)
 
@@ -215,6 +225,9 @@ def load_library():
         "faqcs_inflate_device": (i32, [vp, vp, u64, vp, u32, C.POINTER(InflateOut)]),
         "faqcs_inflate_host": (i32, [vp, u64, vp, u32, C.POINTER(InflateOut)]),
         "faqcs_inflate_time_ms": (i32, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+        "faqcs_deflate_device": (i32, [vp, vp, u64, u32, i32, C.POINTER(DeflateOut)]),
+        "faqcs_deflate_host": (i32, [vp, u64, u32, i32, C.POINTER(DeflateOut)]),
+        "faqcs_deflate_time_ms": (i32, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "faqcs_submit_async": (i32, [vp, C.POINTER(Batch), vp, C.POINTER(u64)]),
         "faqcs_wait": (i32, [vp, u64]),
         "faqcs_host_alloc": (vp, [C.c_size_t]),

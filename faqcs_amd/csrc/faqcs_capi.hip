@@ -19,6 +19,7 @@
 
 #include "faqcs_dev.h"
 #include "faqcs_inflate.h"
+#include "faqcs_deflate.h"
 #include "faqcs_kmer.h"
 #include "faqcs_skm.h"
 
@@ -67,6 +68,9 @@ hipError_t faqcs_launch_render_gather(const faqcs_batch *b, bool trimmed, const 
 size_t faqcs_inflate_scratch_bytes(uint32_t n_members);
 hipError_t faqcs_launch_inflate_scan(const uint8_t *comp, unsigned long long n_comp, const uint32_t *moff, uint32_t n, const faqcs_inflate_out *out, void *scratch, hipStream_t st);
 hipError_t faqcs_launch_inflate_decode(const uint8_t *comp, const uint32_t *moff, uint32_t n, const faqcs_inflate_out *out, void *scratch, int n_cu, hipStream_t st);
+size_t faqcs_deflate_scratch_bytes(uint32_t n, uint32_t n_data, uint32_t member_bytes, int n_cu);
+hipError_t faqcs_launch_deflate_encode(const uint8_t *text, unsigned long long n_text, uint32_t member_bytes, uint32_t n, uint32_t n_data, void *scratch, int n_cu, hipStream_t st);
+hipError_t faqcs_launch_deflate_gather(uint32_t member_bytes, uint32_t n, uint32_t n_data, const faqcs_deflate_out *out, void *scratch, int n_cu, hipStream_t st);
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string &msg) { g_err = msg; return code; }
@@ -155,6 +159,7 @@ struct faqcs_ctx {
     PackStage parse;  // the line index, the record lengths and the two scans' tile sums | index + records, gather
     PackStage render; // the 32-byte descriptor and the text offset of every rendered record, the scan's tile sums | scan, gather
     PackStage inflate; // the header fields, the position and the status of every member, the scan's tile sums | scan, decode
+    PackStage deflate; // every member's slot, size and position, a block's tokens, the scan's tile sums | encode, gather
     // per-read composition records (trim kernel -> composition_histogram).  Two sets: the histogram kernels of
     // submission k run on the aux stream next to the trim kernel of submission k+1 (LDS-bound next to VALU-bound).
     struct RecSet { DevBuf<unsigned long long> pre, post; hipEvent_t trimmed = nullptr, folded = nullptr; bool used = false; };
@@ -539,7 +544,7 @@ extern "C" void faqcs_destroy(faqcs_ctx *c)
     for (auto &t : c->timings) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); (void)hipEventDestroy(t.p); (void)hipEventDestroy(t.k0); (void)hipEventDestroy(t.k1); }
     if (c->comm) comm_release(c->comm);
     if (c->comm_ev) (void)hipEventDestroy(c->comm_ev);
-    c->emit.release(); c->parse.release(); c->render.release(); c->inflate.release();
+    c->emit.release(); c->parse.release(); c->render.release(); c->inflate.release(); c->deflate.release();
     if (c->ins_a) (void)hipEventDestroy(c->ins_a);
     if (c->ins_b) (void)hipEventDestroy(c->ins_b);
     for (int k = 0; k < 2; ++k) { if (c->fwd_free[k]) (void)hipEventDestroy(c->fwd_free[k]); if (c->fwd_copied[k]) (void)hipEventDestroy(c->fwd_copied[k]); c->fwd_items[k].release(); }
@@ -1568,6 +1573,77 @@ extern "C" int faqcs_inflate_host(const uint8_t *comp, uint64_t n_comp, const ui
             }
             pos += isz;
             if (out->member_text_offset) out->member_text_offset[k + 1] = (uint32_t)pos;
+        }
+    }
+    *out->info = info;
+    return 0;
+}
+
+static int deflate_check_args(const char *who, const uint8_t *text, uint64_t n_text, uint32_t member_bytes, int final, const faqcs_deflate_out *out)
+{
+    const std::string w(who);
+    if (!out || !out->comp || !out->info) return fail(FAQCS_E_INVAL, w + ": null output, comp or info");
+    if (!text && n_text) return fail(FAQCS_E_INVAL, w + ": null text");
+    if ((uintptr_t)out->comp & 15u) return fail(FAQCS_E_INVAL, w + ": the output must be 16-byte aligned");
+    if (n_text >= (1ull << 32)) return fail(FAQCS_E_INVAL, w + ": 2^32 bytes of text or more must be cut into chunks (final = 0)");
+    if (member_bytes > faqcs_deflate::MAX_TEXT) return fail(FAQCS_E_INVAL, w + ": a member holds at most 65 280 bytes of text");
+    const uint64_t mb = member_bytes ? member_bytes : (uint64_t)faqcs_deflate::MAX_TEXT;
+    if ((n_text + mb - 1) / mb + (final ? 1u : 0u) > 0xffffffffull) return fail(FAQCS_E_INVAL, w + ": 2^32 members or more (the member count is 32 bits wide)");
+    return 0;
+}
+
+extern "C" int faqcs_deflate_device(faqcs_ctx *c, const uint8_t *d_text, uint64_t n_text, uint32_t member_bytes, int final, const faqcs_deflate_out *out)
+{
+    if (!c) return fail(FAQCS_E_INVAL, "null ctx");
+    if (int rc = deflate_check_args("faqcs_deflate_device", d_text, n_text, member_bytes, final, out)) return rc;
+    const uint32_t mb = member_bytes ? member_bytes : (uint32_t)faqcs_deflate::MAX_TEXT;
+    const uint32_t n_data = (uint32_t)((n_text + mb - 1) / mb), n = n_data + (final ? 1u : 0u);
+    if (int rc = c->deflate.begin(c, faqcs_deflate_scratch_bytes(n, n_data, mb, c->n_cu))) return rc;
+    HIPCHK(faqcs_launch_deflate_encode(d_text, n_text, mb, n, n_data, c->deflate.scratch.p, c->n_cu, c->compute));
+    if (int rc = c->deflate.mark(1)) return rc;
+    HIPCHK(faqcs_launch_deflate_gather(mb, n, n_data, out, c->deflate.scratch.p, c->n_cu, c->compute));
+    return c->deflate.mark(2);
+}
+
+extern "C" int faqcs_deflate_time_ms(faqcs_ctx *c, double *encode_ms, double *gather_ms)
+{
+    if (!c || !encode_ms || !gather_ms) return fail(FAQCS_E_INVAL, "null argument");
+    return c->deflate.times(c, "faqcs_deflate_time_ms: no deflate on this context yet", encode_ms, gather_ms);
+}
+
+// The host statement of the deflate rules (include/faqcs_mi.h at faqcs_deflate_device): every member by the encoder text of the kernel into
+// a slot of its own, then -- when the total fits -- the members back to back, so that exactly comp[0 .. n_bytes) is written.
+extern "C" int faqcs_deflate_host(const uint8_t *text, uint64_t n_text, uint32_t member_bytes, int final, const faqcs_deflate_out *out)
+{
+    namespace def = faqcs_deflate;
+    if (int rc = deflate_check_args("faqcs_deflate_host", text, n_text, member_bytes, final, out)) return rc;
+    const uint32_t mb = member_bytes ? member_bytes : (uint32_t)def::MAX_TEXT;
+    const uint32_t n_data = (uint32_t)((n_text + mb - 1) / mb), n = n_data + (final ? 1u : 0u);
+    std::unique_ptr<def::Work> W(new def::Work);
+    std::vector<uint32_t> tok((mb + def::TILE - 1) / def::TILE * def::TILE);
+    std::vector<uint8_t> slot(def::slot_bytes(mb)), all;
+    std::vector<uint32_t> ends(n);
+    def::HostExec X;
+    faqcs_deflate_info info{};
+    for (uint32_t k = 0; k < n_data; ++k) {
+        const uint64_t a = (uint64_t)k * mb;
+        const uint32_t len = (uint32_t)std::min<uint64_t>(mb, n_text - a);
+        const uint32_t r = def::deflate_member(X, *W, text + a, len, tok.data(), slot.data());
+        info.n_stored += r >> 31;
+        all.insert(all.end(), slot.begin(), slot.begin() + (r & 0x7fffffffu));
+        ends[k] = (uint32_t)all.size();
+    }
+    if (final) {
+        for (uint32_t i = 0; i < def::EOF_BYTES; ++i) all.push_back((uint8_t)def::eof_byte(i));
+        ends[n_data] = (uint32_t)all.size();
+    }
+    info.n_bytes = all.size(); info.n_members = n;
+    info.overflow = (all.size() > out->capacity_bytes || all.size() >= (1ull << 32)) ? 1u : 0u;
+    if (!info.overflow) {
+        if (!all.empty()) memcpy(out->comp, all.data(), all.size());
+        if (out->member_offset) {
+            out->member_offset[0] = 0;
+            for (uint32_t k = 0; k < n; ++k) out->member_offset[k + 1] = ends[k];
         }
     }
     *out->info = info;

@@ -1,5 +1,5 @@
 """Torch-facing helpers of the device seam: inputs and outputs are torch tensors that live on the GPU; the work is the
-library's HIP kernels (faqcs_emit_device, faqcs_render_device, faqcs_inflate_device), never torch ops."""
+library's HIP kernels (faqcs_emit_device, faqcs_render_device, faqcs_inflate_device, faqcs_deflate_device), never torch ops."""
 import ctypes as C
 
 from . import _capi as capi
@@ -122,3 +122,37 @@ def inflated_text(engine, comp, member_offset=None, capacity=None):
         raise FaqcsError(capi.E_INVAL, "member %d: %s" % (n_mem, engine.lib.faqcs_inflate_error_text(error).decode()))
     a = front + shift
     return o_text[a:a + n_bytes], o_off[:n_mem + 1]
+
+
+def deflated_bgzf(engine, text, member_bytes=0, final=True, capacity=None):
+    """`text` as BGZF members, compressed on the device (faqcs_deflate_device).
+
+    text: uint8 CUDA tensor (any alignment); member_bytes: text bytes per member (0: 65 280, as bgzip cuts); final: append the EOF member;
+    capacity: bytes to make room for (default: half the text, and the call is repeated once with what info asks for when that is too
+    little).  Returns (comp, member_offset): uint8 [n_bytes], a view that starts 16-byte aligned, and int32 [n_members + 1] (bit pattern of
+    uint32) -- with n_members = len(member_offset) - 1 the arguments faqcs_inflate_device takes."""
+    import torch
+
+    dev = text.device
+    text = text.contiguous()
+    n_text = int(text.numel())
+    mb = int(member_bytes) or 65280
+    n = (n_text + mb - 1) // mb + (1 if final else 0)
+    cap = n_text // 2 + 31 * n + 64 if capacity is None else int(capacity)
+    o_off = torch.empty(n + 1, dtype=torch.int32, device=dev)
+    info = torch.zeros(3, dtype=torch.int64, device=dev)
+    torch.cuda.current_stream(dev).synchronize()  # the library's compute stream is its own: the input must be complete
+    for attempt in range(2):
+        o_comp = torch.empty(cap + capi.ARENA_PAD_AFTER + 32, dtype=torch.uint8, device=dev)
+        shift = (-o_comp.data_ptr()) % 16
+        out = capi.DeflateOut(o_comp.data_ptr() + shift, cap, o_off.data_ptr(), info.data_ptr())
+        torch.cuda.current_stream(dev).synchronize()
+        engine.deflate_device(text.data_ptr() if n_text else None, n_text, int(member_bytes), final, out)
+        engine.sync()
+        h = info.cpu().numpy()
+        n_bytes, n_mem, overflow = int(h[0]), int(h[1]) & 0xFFFFFFFF, int(h[1]) >> 32
+        if not overflow:
+            return o_comp[shift:shift + n_bytes], o_off[:n_mem + 1]
+        if attempt or n_bytes >= 1 << 32:
+            raise FaqcsError(capi.E_INVAL, "faqcs_deflate_device: the members need %d bytes, the output holds %d" % (n_bytes, cap))
+        cap = n_bytes

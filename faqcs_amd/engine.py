@@ -39,6 +39,25 @@ def bgzf_index_host(comp, final=True, lib=None):
     return off[:info.n_members + 1].copy(), int(info.consumed), int(info.error)
 
 
+def deflate_host(text, member_bytes=0, final=True, lib=None):
+    """faqcs_deflate_host (host only, no GPU): `text` (bytes or a uint8 array) as BGZF members of member_bytes bytes of text each (0: 65 280),
+    the EOF member behind them when final.  Returns (comp bytes, member_offset uint32 [n_members + 1], n_stored): the bytes
+    faqcs_deflate_device produces for the same arguments."""
+    lib = lib or capi.load_library()
+    buf = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else np.ascontiguousarray(text, dtype=np.uint8)
+    mb = int(member_bytes) or 65280
+    n = (len(buf) + mb - 1) // mb + (1 if final else 0)
+    cap = len(buf) + 31 * n + 16
+    store = np.zeros(cap + 16, dtype=np.uint8)
+    shift = (-store.ctypes.data) % 16
+    off = np.zeros(n + 1, dtype=np.uint32)
+    info = capi.DeflateInfo()
+    out = capi.DeflateOut(store.ctypes.data + shift, cap, off.ctypes.data, C.addressof(info))
+    _check(lib, lib.faqcs_deflate_host(buf.ctypes.data if len(buf) else None, len(buf), int(member_bytes), 1 if final else 0, C.byref(out)))
+    assert not info.overflow and info.n_members == n
+    return store[shift:shift + info.n_bytes].tobytes(), off, int(info.n_stored)
+
+
 class HipEngine:
     name = "hip"
 
@@ -115,6 +134,18 @@ class HipEngine:
         """(scan ms, decode ms) of the last inflate_device() on this engine (HIP events on the compute stream); waits for it."""
         a, g = C.c_double(), C.c_double()
         _check(self.lib, self.lib.faqcs_inflate_time_ms(self.ctx, C.byref(a), C.byref(g)))
+        return a.value, g.value
+
+    def deflate_device(self, d_text, n_text, member_bytes, final, out):
+        """faqcs_deflate_device: text in device memory (d_text: device address, any alignment) -> BGZF members of member_bytes bytes of text
+        each (0: 65 280) in the arrays of `out` (a capi.DeflateOut of device pointers), the EOF member behind them when final.
+        Enqueued; sync() waits."""
+        _check(self.lib, self.lib.faqcs_deflate_device(self.ctx, d_text, int(n_text), int(member_bytes), 1 if final else 0, C.byref(out)))
+
+    def deflate_time_ms(self):
+        """(encode ms, gather ms) of the last deflate_device() on this engine (HIP events on the compute stream); waits for it."""
+        a, g = C.c_double(), C.c_double()
+        _check(self.lib, self.lib.faqcs_deflate_time_ms(self.ctx, C.byref(a), C.byref(g)))
         return a.value, g.value
 
     def bgzf_index_host(self, comp, final=True):

@@ -34,7 +34,8 @@ extern "C" {
  * Round 6 adds faqcs_kmer_finish_pass, and faqcs_sync() no longer counts the k-mers that wait in the open group (see below).
  * faqcs_emit_device (the trimmed, edited reads packed on the device) is a new entry point with structures of its own, and so are
  * faqcs_parse_device / faqcs_parse_host (FASTQ text to a packed batch) and faqcs_render_device / faqcs_render_host (the FASTQ text of the
- * output files), and faqcs_inflate_device / faqcs_inflate_host / faqcs_bgzf_index_host (BGZF members to that text). */
+ * output files), and faqcs_inflate_device / faqcs_inflate_host / faqcs_bgzf_index_host (BGZF members to that text),
+ * and faqcs_deflate_device / faqcs_deflate_host (text to BGZF members). */
 #define FAQCS_ABI_VERSION 2
 
 /* FilterStat enum order, FaQCs.h:46-75 */
@@ -424,6 +425,50 @@ int  faqcs_inflate_device(faqcs_ctx *ctx, const uint8_t *d_comp, uint64_t n_comp
                           const faqcs_inflate_out *out);
 int  faqcs_inflate_host(const uint8_t *comp, uint64_t n_comp, const uint32_t *member_offset, uint32_t n_members, const faqcs_inflate_out *out);
 
+/* The step behind the device seam: compressed output.  Text in device memory (what faqcs_render_device() assembled, or any bytes) -> BGZF
+ * members in device memory, so that a third of the bytes leave the card and the result is what faqcs_inflate_device() takes.
+ *   - cutting the text.  The text is cut every member_bytes bytes: member k is text[k * member_bytes .. min(n_text, (k + 1) * member_bytes)).
+ *     member_bytes = 0 means 65 280, as bgzip cuts; valid values are 1 .. 65 280 (the small ones exist so that tests reach every member
+ *     boundary case with little data).
+ *   - a member is exactly what faqcs_inflate_device documents as a MEMBER, and what bgzip, gzip -d and zlib's gzread accept: the 18-byte
+ *     header  1f 8b 08 04 | 00000000 | 00 ff | 06 00 | 'B' 'C' 02 00 | BSIZE,  ONE deflate block -- dynamic, fixed or stored, whichever
+ *     is smallest -- and the trailer, CRC-32 and ISIZE.  A member is never larger than its text + 31 bytes: when the coded form is not
+ *     smaller than a stored block the stored block is written and info->n_stored counts the member; so BSIZE always fits 16 bits.
+ *   - matches have distances 1 .. 32 768 that never reach in front of the member (a 65 280-byte member has earlier positions farther back
+ *     than the format allows: they are refused) and lengths 3 .. 258.
+ *   - final = 1: the 28-byte EOF member of bgzip is appended, and counted in n_members and member_offset.  final = 0: nothing is appended,
+ *     so the outputs of the chunks of a file concatenate to the file.  n_text = 0 yields zeros, or the EOF member alone with final = 1.
+ *   - out->info is ALWAYS complete.  n_bytes > capacity_bytes or n_bytes >= 2^32 sets overflow = 1 and NOTHING but info is written: no
+ *     truncation, ever.  Otherwise only comp[0 .. n_bytes rounded up to 16), member_offset[0 .. n_members] and info are touched.
+ *   - the bytes are a function of (text, member_bytes, final) alone: not of the grid, of timing or of the alignment of d_text (none is
+ *     asked of it, and nothing outside d_text[0 .. n_text) is read), and faqcs_deflate_host produces the same bytes.  The match finder is
+ *     defined without an order of execution (csrc/faqcs_deflate.h): the candidates of a position are the latest
+ *     earlier position with its hash in a 1 024-byte tile in front of its own tile, and the position in front of it; the parse is the
+ *     greedy one.
+ * faqcs_deflate_device: d_text and every pointer of *out (out->info included) are DEVICE pointers.  Enqueued on the context's compute stream,
+ * returns at once; faqcs_sync() waits.  (out->comp, out->member_offset, info->n_members) is what faqcs_inflate_device() takes as (d_comp,
+ * d_member_offset, n_members): no host index is needed.
+ * FAQCS_E_INVAL: n_text >= 2^32, member_bytes > 65 280, a null ctx / out / out->comp / out->info, a null d_text with n_text > 0, out->comp
+ * not 16-byte aligned, 2^32 members or more (2^32 - 1 bytes cut every byte, and the EOF member: n_members is 32 bits wide).  Scratch is the library's, grown on demand and freed by faqcs_destroy(): per member a slot of member_bytes + 31
+ * rounded up to 16 (65 312 bytes at the default cut) and 8 bytes of sizes, per compute unit 4 bytes per position of a member (255 KB).
+ * faqcs_deflate_host is the same call with HOST pointers: the host statement of these rules, single-threaded, no HIP call and no zlib,
+ * built from the same encoder text as the kernel.  It writes exactly comp[0 .. n_bytes). */
+typedef struct faqcs_deflate_info {
+    uint64_t n_bytes;      /* compressed bytes of all members */
+    uint32_t n_members;    /* members, the EOF member included */
+    uint32_t overflow;     /* 1: n_bytes > capacity_bytes or >= 2^32 */
+    uint32_t n_stored;     /* members whose block is a stored one */
+    uint32_t reserved;     /* 0 */
+} faqcs_deflate_info;
+typedef struct faqcs_deflate_out {
+    uint8_t  *comp;            /* 16-byte aligned; capacity_bytes (+ FAQCS_ARENA_PAD_AFTER) writable */
+    uint64_t  capacity_bytes;
+    uint32_t *member_offset;   /* OPTIONAL, n_members + 1: [0] = 0, [k + 1] = end of member k  -- the array faqcs_inflate_device takes */
+    faqcs_deflate_info *info;
+} faqcs_deflate_out;
+int  faqcs_deflate_device(faqcs_ctx *ctx, const uint8_t *d_text, uint64_t n_text, uint32_t member_bytes, int final, const faqcs_deflate_out *out);
+int  faqcs_deflate_host(const uint8_t *text, uint64_t n_text, uint32_t member_bytes, int final, const faqcs_deflate_out *out);
+
 /* Pipelined form of faqcs_submit(): returns a ticket; faqcs_wait(ticket) blocks until THAT batch's results have
  * landed in `results` (later batches may still be in flight: two input staging slots let the H2D copy of batch
  * k+1 overlap the kernels of batch k).  Host arenas / result arrays obtained from faqcs_host_alloc() are pinned,
@@ -558,6 +603,8 @@ int  faqcs_parse_time_ms(faqcs_ctx *ctx, double *index_ms, double *gather_ms);
 int  faqcs_render_time_ms(faqcs_ctx *ctx, double *scan_ms, double *gather_ms);
 /* the same for the LAST faqcs_inflate_device() on the context: the scan of the headers (scan_ms), the decode with its CRC and the status (decode_ms) */
 int  faqcs_inflate_time_ms(faqcs_ctx *ctx, double *scan_ms, double *decode_ms);
+/* the same for the LAST faqcs_deflate_device() on the context: the members' encoding into their slots (encode_ms), sizes, positions and the gather (gather_ms) */
+int  faqcs_deflate_time_ms(faqcs_ctx *ctx, double *encode_ms, double *gather_ms);
 /* diagnostic builds only: section clocks accumulated by the trim kernel (16 words; read and cleared) */
 int  faqcs_debug_words(faqcs_ctx *ctx, uint64_t *out, uint32_t n);
 /* average duration (ms) of the dominant kernel over the launches since the last call, measured with
