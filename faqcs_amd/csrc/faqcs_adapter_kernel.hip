@@ -1476,7 +1476,7 @@ static hipError_t launch_adapter(const AdapterDev &A, const AdapterGroup &G, con
 }
 
 // G == nullptr: the whole set in one pass (at most FAQCS_ADAPTER_GROUP targets of at most FAQCS_ADAPTER_SINGLE_LENGTH bases); else A is
-// one group of a larger library and G its place in the sequence of group launches (faqcs_capi.hip)
+// one group of a larger library and G its place in the sequence of group launches (faqcs_capi.hip: enqueue_adapter)
 hipError_t faqcs_launch_adapter(const AdapterDev &A, const AdapterGroup *G, const uint8_t *seq, const uint32_t *off, uint32_t n_reads,
                                 uint32_t max_len, const uint32_t *seg_start, uint32_t n_segments, uint32_t *ad_sl,
                                 uint16_t *ad_hit, uint64_t *adapter_stats, uint32_t *err, uint32_t dbg, int n_cu, hipStream_t st)

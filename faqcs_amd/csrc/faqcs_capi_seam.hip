@@ -1,0 +1,124 @@
+// faqcs_capi_seam.hip -- the device seams of the C ABI (include/faqcs_mi.h): faqcs_emit_device, faqcs_parse_device, faqcs_render_device,
+// faqcs_inflate_device and faqcs_deflate_device with their faqcs_*_time_ms.  Each is two stages of kernels between the marks of a
+// PackStage; the host statements of the same rules, and the argument checks shared with them, are in faqcs_host.cpp.
+#include "faqcs_ctx.h"
+#include "faqcs_deflate.h"
+
+int PackStage::begin(faqcs_ctx *c, size_t scratch_bytes)
+{
+    HIPCHK(hipSetDevice(c->device));
+    st = c->compute;
+    const size_t need = (scratch_bytes + sizeof(uint4) - 1) / sizeof(uint4);
+    if (need > scratch.cap) HIPCHK(hipStreamSynchronize(st)); // (growing frees the scratch an earlier call may still read)
+    HIPCHK(scratch.reserve(need));
+    for (auto &e : ev) if (!e) HIPCHK(hipEventCreate(&e));
+    return mark(0);
+}
+
+int PackStage::mark(int i)
+{
+    HIPCHK(hipEventRecord(ev[i], st));
+    if (i == 2) timed = true;
+    return 0;
+}
+
+int PackStage::times(faqcs_ctx *c, const char *not_yet, double *first_ms, double *second_ms)
+{
+    if (!timed) return fail(FAQCS_E_INVAL, not_yet);
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipEventSynchronize(ev[2]));
+    float ms[2] = {0.f, 0.f};
+    for (int i = 0; i < 2; ++i) HIPCHK(hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]));
+    *first_ms = ms[0]; *second_ms = ms[1];
+    return 0;
+}
+
+// faqcs_*_time_ms: the two stages of the entry point's last call on the context
+static int stage_times(faqcs_ctx *c, PackStage faqcs_ctx::*stage, const char *not_yet, double *first_ms, double *second_ms)
+{
+    if (!c || !first_ms || !second_ms) return fail(FAQCS_E_INVAL, "null argument");
+    return (c->*stage).times(c, not_yet, first_ms, second_ms);
+}
+
+void PackStage::release()
+{
+    scratch.release();
+    for (auto &e : ev) if (e) (void)hipEventDestroy(e);
+}
+
+extern "C" int faqcs_emit_device(faqcs_ctx *c, const faqcs_batch *b, const faqcs_read_result *d_results, const uint8_t *d_keep, const faqcs_emit_out *out)
+{
+    if (!c) return fail(FAQCS_E_INVAL, "null ctx");
+    if (!b || !d_results || !out) return fail(FAQCS_E_INVAL, "faqcs_emit_device: null batch, results or output");
+    if (!out->seq || !out->qual || !out->offset || !out->info) return fail(FAQCS_E_INVAL, "faqcs_emit_device: null output arena, offset or info");
+    if (((uintptr_t)out->seq | (uintptr_t)out->qual) & 15u) return fail(FAQCS_E_INVAL, "faqcs_emit_device: the output arenas must be 16-byte aligned");
+    const uint32_t n = b->n_reads;
+    if (n && (!b->seq || !b->qual || !b->offset)) return fail(FAQCS_E_INVAL, "faqcs_emit_device: null batch arrays");
+    if (int rc = c->emit.begin(c, faqcs_emit_scratch_bytes(n))) return rc;
+    HIPCHK(faqcs_launch_emit_scan(b->seq, b->offset, b->terminal_n, n, d_results, d_keep, out, c->emit.scratch.p, c->compute));
+    if (int rc = c->emit.mark(1)) return rc;
+    HIPCHK(faqcs_launch_emit_gather(b->seq, b->qual, n, out, c->emit.scratch.p, c->prm.input_quality_offset, c->prm.output_quality_offset,
+                                    c->prm.replace_to_N_q, c->n_cu, c->compute));
+    return c->emit.mark(2);
+}
+
+extern "C" int faqcs_emit_time_ms(faqcs_ctx *c, double *scan_ms, double *gather_ms) { return stage_times(c, &faqcs_ctx::emit, "faqcs_emit_time_ms: no emission on this context yet", scan_ms, gather_ms); }
+
+extern "C" int faqcs_parse_device(faqcs_ctx *c, const uint8_t *d_text, uint64_t n_text, int final, const faqcs_parse_out *out)
+{
+    if (!c) return fail(FAQCS_E_INVAL, "null ctx");
+    if (int rc = parse_check_args("faqcs_parse_device", d_text, n_text, out)) return rc;
+    if (int rc = c->parse.begin(c, faqcs_parse_scratch_bytes(n_text))) return rc;
+    HIPCHK(faqcs_launch_parse_index(d_text, n_text, final ? 1 : 0, c->parse.scratch.p, c->compute));
+    HIPCHK(faqcs_launch_parse_records(d_text, n_text, out, c->parse.scratch.p, c->n_cu, c->compute));
+    if (int rc = c->parse.mark(1)) return rc;
+    HIPCHK(faqcs_launch_parse_gather(d_text, n_text, out, c->parse.scratch.p, c->n_cu, c->compute));
+    return c->parse.mark(2);
+}
+
+extern "C" int faqcs_parse_time_ms(faqcs_ctx *c, double *index_ms, double *gather_ms) { return stage_times(c, &faqcs_ctx::parse, "faqcs_parse_time_ms: no parse on this context yet", index_ms, gather_ms); }
+
+extern "C" int faqcs_render_device(faqcs_ctx *c, const faqcs_batch *b, const faqcs_read_result *d_results, const uint8_t *d_text,
+                                   const uint32_t *d_def_pos, const uint32_t *d_def_len, const uint8_t *d_select, const uint32_t *d_order,
+                                   const faqcs_render_out *out)
+{
+    if (!c) return fail(FAQCS_E_INVAL, "null ctx");
+    if (int rc = render_check_args("faqcs_render_device", b, d_text, d_def_pos, d_def_len, out)) return rc;
+    const uint32_t n = b->n_reads;
+    if (int rc = c->render.begin(c, faqcs_render_scratch_bytes(n))) return rc;
+    HIPCHK(faqcs_launch_render_scan(b, d_results, d_def_pos, d_def_len, d_select, d_order, out, c->render.scratch.p, c->compute));
+    if (int rc = c->render.mark(1)) return rc;
+    HIPCHK(faqcs_launch_render_gather(b, d_results != nullptr, d_text, out, c->render.scratch.p, c->prm.input_quality_offset, c->prm.output_quality_offset,
+                                      c->prm.replace_to_N_q, c->n_cu, c->compute));
+    return c->render.mark(2);
+}
+
+extern "C" int faqcs_render_time_ms(faqcs_ctx *c, double *scan_ms, double *gather_ms) { return stage_times(c, &faqcs_ctx::render, "faqcs_render_time_ms: no rendering on this context yet", scan_ms, gather_ms); }
+
+extern "C" int faqcs_inflate_device(faqcs_ctx *c, const uint8_t *d_comp, uint64_t n_comp, const uint32_t *d_member_offset, uint32_t n_members, const faqcs_inflate_out *out)
+{
+    if (!c) return fail(FAQCS_E_INVAL, "null ctx");
+    if (int rc = inflate_check_args("faqcs_inflate_device", d_comp, n_comp, d_member_offset, n_members, out)) return rc;
+    if (int rc = c->inflate.begin(c, faqcs_inflate_scratch_bytes(n_members))) return rc;
+    HIPCHK(faqcs_launch_inflate_scan(d_comp, n_comp, d_member_offset, n_members, out, c->inflate.scratch.p, c->compute));
+    if (int rc = c->inflate.mark(1)) return rc;
+    HIPCHK(faqcs_launch_inflate_decode(d_comp, d_member_offset, n_members, out, c->inflate.scratch.p, c->n_cu, c->compute));
+    return c->inflate.mark(2);
+}
+
+extern "C" int faqcs_inflate_time_ms(faqcs_ctx *c, double *scan_ms, double *decode_ms) { return stage_times(c, &faqcs_ctx::inflate, "faqcs_inflate_time_ms: no inflate on this context yet", scan_ms, decode_ms); }
+
+extern "C" int faqcs_deflate_device(faqcs_ctx *c, const uint8_t *d_text, uint64_t n_text, uint32_t member_bytes, int final, const faqcs_deflate_out *out)
+{
+    if (!c) return fail(FAQCS_E_INVAL, "null ctx");
+    if (int rc = deflate_check_args("faqcs_deflate_device", d_text, n_text, member_bytes, final, out)) return rc;
+    const uint32_t mb = member_bytes ? member_bytes : (uint32_t)faqcs_deflate::MAX_TEXT;
+    const uint32_t n_data = (uint32_t)((n_text + mb - 1) / mb), n = n_data + (final ? 1u : 0u);
+    if (int rc = c->deflate.begin(c, faqcs_deflate_scratch_bytes(n, n_data, mb, c->n_cu))) return rc;
+    HIPCHK(faqcs_launch_deflate_encode(d_text, n_text, mb, n, n_data, c->deflate.scratch.p, c->n_cu, c->compute));
+    if (int rc = c->deflate.mark(1)) return rc;
+    HIPCHK(faqcs_launch_deflate_gather(mb, n, n_data, out, c->deflate.scratch.p, c->n_cu, c->compute));
+    return c->deflate.mark(2);
+}
+
+extern "C" int faqcs_deflate_time_ms(faqcs_ctx *c, double *encode_ms, double *gather_ms) { return stage_times(c, &faqcs_ctx::deflate, "faqcs_deflate_time_ms: no deflate on this context yet", encode_ms, gather_ms); }

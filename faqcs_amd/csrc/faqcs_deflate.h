@@ -1,5 +1,5 @@
 // faqcs_deflate.h -- the encoder core of faqcs_deflate_device / faqcs_deflate_host (include/faqcs_mi.h): one BGZF
-// member from at most 65 280 bytes of text.  The SAME text compiles for the host (faqcs_capi.hip: faqcs_deflate_host;
+// member from at most 65 280 bytes of text.  The SAME text compiles for the host (faqcs_host.cpp: faqcs_deflate_host;
 // tools/deflate_host_fuzz.cpp under the sanitizers) and for gfx950 (faqcs_deflate_kernel.hip), the way faqcs_inflate.h does, and the bytes it
 // produces are a function of the text alone: every step is either per-position work whose result does not depend on who does it, or a
 // commutative update (max, add, or) of a shared word, or serial work of lane 0.  No HIP call, no zlib.

@@ -1,4 +1,4 @@
-// faqcs_dev.h -- shared between the host side (faqcs_capi.hip) and the gfx950 kernels.
+// faqcs_dev.h -- shared between the host side (faqcs_ctx.h, faqcs_capi*.hip) and the gfx950 kernels.
 //
 // Data layout in HBM:
 //   seq / qual      byte arenas, reads packed back to back, read i = [offset[i], offset[i+1])

@@ -1,6 +1,6 @@
 // faqcs_emit_kernel.hip -- faqcs_emit_device(): the trimmed, edited reads of a device-resident batch, packed back to back on the device.
 //
-// What one emitted read holds is what faqcs_apply_edits() (faqcs_capi.hip) writes for it: the kept window [start, start + len) of the read,
+// What one emitted read holds is what faqcs_apply_edits() (faqcs_host.cpp) writes for it: the kept window [start, start + len) of the read,
 // 'G' -> 'N' below --replace_to_N_q (trim.cpp:390-403), the quality of the read's leading / trailing upper-case 'N' runs set to the input
 // offset (trim.cpp:1191-1216), the quality re-based from the input to the output offset (trim.cpp:516-525).
 //

@@ -1,0 +1,18 @@
+// faqcs_host.h -- what faqcs_host.cpp (plain host C++, no HIP) shares with the device side of the library (faqcs_ctx.h): the one error
+// sink behind faqcs_last_error() and the argument checks that a host statement and its device entry point both make.  Internal: nothing
+// declared here is exported.
+#pragma once
+#include <string>
+
+#include "../../include/faqcs_mi.h"
+
+#define FAQCS_HIDDEN __attribute__((visibility("hidden")))
+
+// stores the calling thread's message (faqcs_last_error) and returns `code`
+FAQCS_HIDDEN int fail(int code, const std::string &msg);
+
+// `who` names the entry point in the message
+FAQCS_HIDDEN int parse_check_args(const char *who, const uint8_t *text, uint64_t n_text, const faqcs_parse_out *out);
+FAQCS_HIDDEN int render_check_args(const char *who, const faqcs_batch *b, const uint8_t *text, const uint32_t *def_pos, const uint32_t *def_len, const faqcs_render_out *out);
+FAQCS_HIDDEN int inflate_check_args(const char *who, const uint8_t *comp, uint64_t n_comp, const uint32_t *member_offset, uint32_t n_members, const faqcs_inflate_out *out);
+FAQCS_HIDDEN int deflate_check_args(const char *who, const uint8_t *text, uint64_t n_text, uint32_t member_bytes, int final, const faqcs_deflate_out *out);

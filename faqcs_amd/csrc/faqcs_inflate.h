@@ -1,6 +1,6 @@
 // faqcs_inflate.h -- the decoder core of faqcs_inflate_device / faqcs_inflate_host (include/faqcs_mi.h): BGZF member header, canonical
 // Huffman tables with zlib's acceptance rules, symbol decode, length / distance arithmetic, the block loop and the CRC-32 arithmetic.
-// The SAME text compiles for the host (faqcs_capi.hip: faqcs_inflate_host; tools/inflate_host_fuzz.cpp under the sanitizers) and for
+// The SAME text compiles for the host (faqcs_host.cpp: faqcs_inflate_host; tools/inflate_host_fuzz.cpp under the sanitizers) and for
 // gfx950 (faqcs_inflate_kernel.hip), the way faqcs_skm.h does: every bound the decoder checks -- input that runs out, a distance in
 // front of the member, output beyond ISIZE -- is checked HERE, before a Sink is asked to move a byte, so what the CPU tests and the
 // sanitizers prove about the arithmetic holds for the device code.  No HIP call, no zlib.

@@ -1,5 +1,5 @@
 // faqcs_kmer.h -- structures and device helpers shared by the k-mer kernels (faqcs_kmer_kernel.hip: the table, the
-// per-occurrence diagnostic path; faqcs_kmer_skm_kernel.hip: super-k-mers, combine-before-insert) and the host side (faqcs_capi.hip).
+// per-occurrence diagnostic path; faqcs_kmer_skm_kernel.hip: super-k-mers, combine-before-insert) and the host side (faqcs_capi_kmer.hip).
 //
 // Replaces update_kmer() (trim.cpp:887-931) and the std::unordered_map<size_t,size_t> tables (trim.cpp:82,133-135).
 #pragma once

@@ -1,4 +1,4 @@
-"""sha256 over the sources libfaqcs_mi.so is built from (faqcs_amd/csrc/*.hip, *.h, include/*.h): what ties a stored counter file
+"""sha256 over the sources libfaqcs_mi.so is built from (faqcs_amd/csrc/*.hip, *.h, faqcs_host.cpp, include/*.h): what ties a stored counter file
 (profiles/traffic_*.json, *_counters.json) to the build it was measured on.  `python tools/source_hash.py` prints it.
 faqcs_pargz.h is not among them: it is host code of the command line (faqcs_cli.cpp includes it, the library does not)."""
 import glob
@@ -13,7 +13,7 @@ HOST_ONLY = {"faqcs_pargz.h"}  # headers under csrc/ that only faqcs_cli.cpp inc
 def source_hash():
     h = hashlib.sha256()
     files = sorted(glob.glob(os.path.join(ROOT, "faqcs_amd", "csrc", "*.hip")) + glob.glob(os.path.join(ROOT, "faqcs_amd", "csrc", "*.h"))
-                   + glob.glob(os.path.join(ROOT, "include", "*.h")))
+                   + [os.path.join(ROOT, "faqcs_amd", "csrc", "faqcs_host.cpp")] + glob.glob(os.path.join(ROOT, "include", "*.h")))
     files = [f for f in files if os.path.basename(f) not in HOST_ONLY]
     for f in files:
         h.update(os.path.basename(f).encode())
