@@ -383,7 +383,12 @@ int  faqcs_render_host(const faqcs_params *p, const faqcs_batch *batch, const fa
  *                     rules above (or offsets that are not increasing inside n_comp) is E_HEADER of that member, ISIZE > 65 536 E_LENGTH.
  *   after decoding    a decoded length that differs from ISIZE is E_LENGTH; an invalid code or code set, block type 3, a stored block with
  *                     LEN != ~NLEN, a distance in front of the member, input that runs out or is left over is E_DATA; a CRC that differs
- *                     from the trailer is E_CRC.
+ *                     from the trailer is E_CRC.  Where a member has more than one of these wrong, the stream is read in order and the first
+ *                     thing met decides: a token (a literal, a match, a stored block) that would carry the text beyond ISIZE is E_LENGTH
+ *                     there and then -- what follows is not read -- and a stream that ends short of ISIZE is E_LENGTH only if it ends
+ *                     well, in the byte in front of the trailer; input that runs out is E_DATA however much text there was.  Within one
+ *                     token E_DATA goes first: a match that leaves ISIZE behind AND starts in front of the member, a stored block whose
+ *                     LEN exceeds ISIZE AND the input, are E_DATA.  E_CRC is looked at last, when stream and length were sound.
  *   Errors are sequential, as in the parse: the first bad member in input order decides, info->n_members is its index, info->n_bytes the
  *   text of the members in front of it, and that text is delivered byte-exact (what lies behind it in `text` is unspecified).  Without an
  *   error n_members and n_bytes are the totals.  The kernels touch only text[0 .. scanned total rounded up to 16), member_text_offset

@@ -10,6 +10,10 @@
 //   - of each, damaged copies (bit flips anywhere in the member, trailer changes, a cut deflate stream): the verdict is never ST_OK unless
 //     zlib accepts the same bytes with the same text, CRC and length; whatever the bytes say, nothing outside the buffers is touched
 //   - the BSIZE walk over the concatenation, cut at random places, with final = 0 / 1
+//   usage: inflate_host_fuzz --corpus FILE
+//   - FILE holds a count, then that many members, each behind its size (32-bit little-endian values): members written elsewhere -- the
+//     catalogue of tests/deflate_streams.py, streams zlib's encoder never writes -- each through the same check as a damaged copy: the
+//     verdict is ST_OK exactly when zlib accepts the bytes, then with zlib's text; nothing outside the exact-size buffers is touched
 #include <zlib.h>
 
 #include <cstdint>
@@ -158,8 +162,33 @@ static void check(const Bytes &m, const Bytes *want, const char *what)
     if (st) ++n_refused; else ++n_ok;
 }
 
+static int run_corpus(const char *path)
+{
+    FILE *f = fopen(path, "rb");
+    if (!f) { printf("FAIL: cannot open %s\n", path); return 1; }
+    uint8_t w[4];
+    if (fread(w, 1, 4, f) != 4) { printf("FAIL: %s holds no count\n", path); return 1; }
+    const uint32_t n = inf::le32(w);
+    for (uint32_t i = 0; i < n; ++i) {
+        if (fread(w, 1, 4, f) != 4) { printf("FAIL: %s ends in front of member %u\n", path, i); return 1; }
+        Bytes m(inf::le32(w));
+        if (m.size() > (1u << 20) || fread(m.data(), 1, m.size(), f) != m.size()) { printf("FAIL: %s ends inside member %u\n", path, i); return 1; }
+        const std::string what = "corpus member " + std::to_string(i);
+        check(m, nullptr, what.c_str());
+    }
+    fclose(f);
+    printf("%u corpus members: %llu accepted with zlib's text, %llu refused as zlib refuses them\n", n, n_ok, n_refused);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
+    if (argc > 2 && !strcmp(argv[1], "--corpus")) {
+        T.reset(new inf::Tables);
+        inf::HostSink S{nullptr};
+        inf::crc_init(*T, S);
+        return run_corpus(argv[2]);
+    }
     const unsigned long long seed = argc > 1 ? strtoull(argv[1], nullptr, 10) : 1;
     const int n = argc > 2 ? atoi(argv[2]) : 100;
     rng.seed(seed);
