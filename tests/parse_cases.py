@@ -129,9 +129,10 @@ def assert_untouched(o, nb, n, round16):
         assert (o[name][n if o["with_def"] else 0:] == CAN32).all(), name + "[] behind the records was written"
 
 
-def assert_parse(o, text, final, round16, what=""):
-    """One parse (parse_host's dict, or the device's in the same form) against driver.parse_model, info field by field."""
-    seq, qual, offset, tn, dpos, dlen, consumed, error = driver.parse_model(text, final)
+def assert_parse(o, text, final, round16, what="", model=None):
+    """One parse (parse_host's dict, or the device's in the same form) against driver.parse_model, info field by field.  model: what
+    driver.parse_model(text, final) returned, when the caller holds one text against several parses."""
+    seq, qual, offset, tn, dpos, dlen, consumed, error = driver.parse_model(text, final) if model is None else model
     n, nb = len(offset) - 1, len(seq)
     lens = np.diff(offset.astype(np.int64))
     want = {"n_bytes": nb, "consumed": consumed, "n_reads": n, "max_read_len": int(lens.max()) if n else 0, "overflow": 0, "error": error}

@@ -25,19 +25,21 @@ def eng():
     e.close()
 
 
-def device_text(text, shift=0):
-    """The text in device memory, hostile bytes ('\\n', '\\r') in the padding either side; `shift` moves it off 16-byte alignment."""
+def device_text(text, shift=0, pad=None):
+    """The text in device memory, hostile bytes ('\\n', '\\r') in the padding either side; `shift` moves it off 16-byte alignment.  pad: one
+    byte value for the whole padding (10 or 13) in place of the two alternating."""
     import torch
 
     dev = torch.device("cuda:0")
-    host = np.full(TEXT_FRONT + shift + len(text) + capi.ARENA_PAD_AFTER, 10, np.uint8)
-    host[1::2] = 13
+    host = np.full(TEXT_FRONT + shift + len(text) + capi.ARENA_PAD_AFTER, 10 if pad is None else pad, np.uint8)
+    if pad is None:
+        host[1::2] = 13
     host[TEXT_FRONT + shift:TEXT_FRONT + shift + len(text)] = np.frombuffer(text, np.uint8)
     t = torch.from_numpy(host).to(dev)
     return t, t.data_ptr() + TEXT_FRONT + shift
 
 
-def parse_device(eng, text, final, cap_bytes=None, cap_reads=None, with_def=True, shift=0, keep=False):
+def parse_device(eng, text, final, cap_bytes=None, cap_reads=None, with_def=True, shift=0, keep=False, pad=None):
     """One faqcs_parse_device into canary-filled device buffers; everything comes back as host arrays (the WHOLE buffers), in the form of
     parse_cases.parse_host."""
     import torch
@@ -46,7 +48,7 @@ def parse_device(eng, text, final, cap_bytes=None, cap_reads=None, with_def=True
     dev = torch.device("cuda:0")
     cap_bytes = len(text) // 2 + 8 if cap_bytes is None else cap_bytes
     cap_reads = len(text) // 4 + 8 if cap_reads is None else cap_reads
-    t_text, d_text = device_text(text, shift)
+    t_text, d_text = device_text(text, shift, pad)
     seq = torch.full((pc.FRONT + cap_bytes + capi.ARENA_PAD_AFTER,), pc.CANARY, dtype=torch.uint8, device=dev)
     qual = torch.full_like(seq, pc.CANARY)
     can32 = -0x5A5A5A5B

@@ -82,8 +82,8 @@ def render(eng, dc, with_res, select, order, tn=True, with_offset=True, with_ind
             "with_offset": with_offset, "with_index": with_index, "exact": False}
 
 
-def host_statement(lib, holder, case, with_res, select, order):
-    o = rc.render_host(lib, holder, case, with_res, select, order)
+def host_statement(lib, holder, case, with_res, select, order, capacity=None):
+    o = rc.render_host(lib, holder, case, with_res, select, order, capacity=capacity)
     assert o["overflow"] == 0
     nb, nr = o["n_bytes"], o["n_reads"]
     return o["text"][o["base"]:o["base"] + nb].copy(), o["rec_offset"][:nr + 1].copy(), o["rec_index"][:nr].copy()
