@@ -310,39 +310,47 @@ static int enqueue_adapter(faqcs_ctx *c, Timing &t, const Submission &s)
     return 0;
 }
 
-// the trim launch.  The composition records of a launch are folded one launch LATE (faqcs_ctx::pending_fold): by this launch's blocks
-// as they run out of reads, else by composition_histogram on the aux stream beside it.
+// an environment switch that is on unless set to 0
+static bool env_on(const char *name) { const char *e = getenv(name); return !e || atoi(e) != 0; }
+
+// the trim launch: trim_plan() (faqcs_trim_plan.h) says which kernel, in which shape, how many records, and who folds.  The composition
+// records of a launch are folded one launch LATE (faqcs_ctx::pending_fold): by this launch's blocks as they run out of reads, else by
+// composition_histogram on the aux stream beside it.
 static int enqueue_trim(faqcs_ctx *c, Timing &t, const Submission &s, const uint32_t *d_sl, const uint16_t *d_hit)
 {
-    const uint32_t n = s.n, max_len = s.max_len;
+    const uint32_t n = s.n;
     HIPCHK(hipEventRecord(t.a, c->compute));
-    const bool wide = max_len > 256; // the long-read kernels write two-word composition records
+    // the records of the launch BEFORE this one: this launch's blocks fold them when they run out of reads, if its kernel can (trim_lds with
+    // a block of at least 122 KB of LDS: the 2x100 ... 2x150 variants); FAQCS_TAIL_FOLD=0: never (A/B)
+    static const bool tail_on = env_on("FAQCS_TAIL_FOLD");
+    const bool offer_fold = c->pending_fold >= 0 && !c->pending_wide && tail_on;
+    DevParams dp = c->dp;
+    dp.fold_n = offer_fold ? c->pending_n : 0u;
+    static const bool lds_on = env_on("FAQCS_TRIM_LDS"), lds4_on = env_on("FAQCS_TRIM_LDS4"), lds16_on = env_on("FAQCS_TRIM_LDS16"); // (once per process)
+    const char *e_long = getenv("FAQCS_TRIM_LONG"); // (read at every submission: a test turns it on for one engine)
+    const TrimPlan plan = trim_plan(trim_options(dp), s.max_len, n, c->n_cu, TrimSwitches{e_long && atoi(e_long) != 0, lds_on, lds4_on, lds16_on});
+    const bool long_reads = plan.kernel == TrimKernel::trim_long; // composition bins are added by the kernel itself, no records
+    dp.wide_records = plan.wide_records;
     const int set = (int)(c->n_enqueued++ & 1);
     faqcs_ctx::RecSet &rs = c->rec[set];
     if (rs.used) { HIPCHK(hipStreamWaitEvent(c->compute, rs.folded, 0)); rs.used = false; } // (a fold of the set's previous records on the aux stream)
-    const char *e_long = getenv("FAQCS_TRIM_LONG"); // (read at every submission: a test turns it on for one engine)
-    const bool force_long = e_long && atoi(e_long) != 0;
-    const bool long_reads = max_len > FAQCS_FAST_READ_LENGTH || force_long; // trim_long: composition bins are added by the kernel itself, no records
-    const size_t need = long_reads ? (size_t)n / 2 + 1 : (size_t)n * (wide ? 2 : 1); // (trim_long: rec_pre is its scratch, one u32 per read)
+    const size_t need = plan.records_needed;
     if (need > rs.pre.cap) { HIPCHK(hipStreamSynchronize(c->aux)); HIPCHK(hipStreamSynchronize(c->compute)); } // (the set's old records may still be read: by the fold kernel, or by the launch before this one)
     HIPCHK(rs.pre.reserve(need)); HIPCHK(rs.post.reserve(need));
-    // the records of the launch BEFORE this one: this launch's blocks fold them when they run out of reads, if its kernel can (trim_lds with
-    // a block of at least 122 KB of LDS: the 2x100 ... 2x150 variants); FAQCS_TAIL_FOLD=0: never (A/B)
-    DevParams dp = c->dp;
-    static const bool tail_on = [] { const char *e = getenv("FAQCS_TAIL_FOLD"); return !e || atoi(e) != 0; }();
-    if (c->pending_fold >= 0 && !c->pending_wide && tail_on) {
+    if (offer_fold) {
         const faqcs_ctx::RecSet &ps = c->rec[c->pending_fold];
         if (!c->d_fold_claim) HIPCHK(hipMalloc((void **)&c->d_fold_claim, 8));
         HIPCHK(hipMemsetAsync(c->d_fold_claim, 0, 8, c->compute));
-        dp.fold_pre = ps.pre.p; dp.fold_post = ps.post.p; dp.fold_n = c->pending_n; dp.fold_claim = c->d_fold_claim;
+        dp.fold_pre = ps.pre.p; dp.fold_post = ps.post.p; dp.fold_claim = c->d_fold_claim;
         dp.fold_dst_pre = c->d_counters + c->lay.pre_comp; dp.fold_dst_post = c->d_counters + c->lay.post_comp;
     }
-    HIPCHK(faqcs_launch_trim(dp, s.seq, s.qual, s.off, n, max_len, d_sl, d_hit, s.res, rs.pre.p, rs.post.p,
-                             c->d_counters, c->d_err, c->n_cu, c->compute, s.tn));
+    const TrimArgs a{s.seq, s.qual, s.off, n, s.max_len, d_sl, d_hit, s.tn, s.res, rs.pre.p, rs.post.p, c->d_counters, c->d_err, c->n_cu, c->compute};
+    HIPCHK(long_reads ? faqcs_launch_trim_long(plan, dp, a)
+                      : plan.kernel == TrimKernel::trim_lds ? faqcs_launch_trim_lds(plan, dp, a) : faqcs_launch_trim_filter_accumulate(plan, dp, a));
     HIPCHK(hipEventRecord(t.b, c->compute));
-    c->trim_kernel = faqcs_last_trim_kernel();
+    c->trim_kernel = trim_kernel_name(plan.kernel);
     if (c->pending_fold >= 0) { // ... else composition_histogram folds them on the aux stream, beside this launch
-        if (!(dp.fold_n && faqcs_last_trim_folded())) {
+        if (!plan.folds_tail) {
             faqcs_ctx::RecSet &ps = c->rec[c->pending_fold];
             HIPCHK(hipStreamWaitEvent(c->aux, ps.trimmed, 0));
             HIPCHK(faqcs_launch_composition(ps.pre.p, ps.post.p, c->pending_n, c->pending_wide, c->d_norm, c->d_counters + c->lay.pre_comp,
@@ -355,7 +363,7 @@ static int enqueue_trim(faqcs_ctx *c, Timing &t, const Submission &s, const uint
     static const bool no_comp = [] { const char *e = getenv("FAQCS_DIAG_NO_COMPOSITION"); return e && atoi(e) != 0; }(); // (diagnostic, wrong composition tables: what the fold costs a step)
     if (!(c->dp.dbg & 1u) && !long_reads && !no_comp) {
         HIPCHK(hipEventRecord(rs.trimmed, c->compute));
-        c->pending_fold = set; c->pending_n = n; c->pending_wide = wide;
+        c->pending_fold = set; c->pending_n = n; c->pending_wide = plan.wide_records;
     }
     return 0;
 }

@@ -33,12 +33,10 @@ struct AdapterDev { // (field by field in faqcs_adapter_kernel.hip)
     float match_rate;
     uint32_t longest, plane_dwords;
 };
-const char *faqcs_last_trim_kernel();
-bool faqcs_last_trim_folded();
-hipError_t faqcs_launch_trim(const DevParams &P, const uint8_t *seq, const uint8_t *qual, const uint32_t *off,
-                             uint32_t n_reads, uint32_t max_len, const uint32_t *ad_sl, const uint16_t *ad_hit,
-                             faqcs_read_result *out, unsigned long long *rec_pre, unsigned long long *rec_post,
-                             uint64_t *counters, uint32_t *err, int n_cu, hipStream_t st, const uint8_t *tn_flags);
+// the trim launchers, one per kernel file: each executes a TrimPlan (trim_plan(), faqcs_trim_plan.h) that names its kernel
+hipError_t faqcs_launch_trim_lds(const TrimPlan &plan, const DevParams &P, const TrimArgs &a);
+hipError_t faqcs_launch_trim_filter_accumulate(const TrimPlan &plan, const DevParams &P, const TrimArgs &a);
+hipError_t faqcs_launch_trim_long(const TrimPlan &plan, const DevParams &P, const TrimArgs &a);
 hipError_t faqcs_launch_terminal_n_flags(const uint8_t *seq, const uint32_t *off, uint32_t n_reads, uint8_t *flags, hipStream_t st);
 hipError_t faqcs_launch_composition(const unsigned long long *rec_pre, const unsigned long long *rec_post, uint32_t n, bool wide,
                                     const float *comp_norm, uint64_t *dst_pre, uint64_t *dst_post, int n_cu, hipStream_t st);

@@ -14,9 +14,9 @@
 #include <stdint.h>
 
 #include "../../include/faqcs_mi.h"
+#include "faqcs_trim_plan.h"
 
 #define FAQCS_WAVE 64
-#define FAQCS_FAST_READ_LENGTH 1024 /* longest read the chunked trim kernels and composition_histogram take; longer reads: trim_long */
 #define FAQCS_TAB_LEN FAQCS_FAST_READ_LENGTH /* per-length lookup tables: every length the chunked kernels support */
 
 // Everything the kernels need from faqcs_params + host-precomputed integer lookup tables, passed by value.
@@ -27,7 +27,7 @@ struct DevParams {
     uint32_t R;                   // row capacity of the global matrices
     uint32_t n_adapters;
     uint32_t dbg;                 // FAQCS_DBG ablation bits (diagnostics only; 0 in production)
-    uint32_t wide_records;        // (set per launch by faqcs_launch_trim_lds) the batch's longest read has more than 256 bases: two-word composition records
+    uint32_t wide_records;        // (set per launch from TrimPlan::wide_records) the batch's longest read has more than 256 bases: two-word composition records
     float lc_ratio, avg_q;        // --lc / --avg_q as given (trim_long evaluates the reference's float expressions directly; the chunked
                                   // kernels use the per-length integer tables below)
     // per-length tables, index 0..FAQCS_TAB_LEN (float32 semantics folded into integers on the host)
@@ -72,9 +72,25 @@ struct AdapterGroup {
     uint32_t last;          // the last group: find_mask_range, credit, ad_sl / ad_hit / err
 };
 
-enum { FS_SLOTS = 32 };
 enum { FAQCS_PARTIAL_ROW = 16896 };  // >= N_ZERO of every trim_lds variant (RowCfg<19, 8, 160>: 7 962, <16, 16, 288>: 13 792, <19, 16, 352>: 16 768): dwords of one flushed copy of a block's LDS accumulators
-enum { FAQCS_PARTIAL_FLUSHES = 8 };  // flushes (rows) a block has room for in one launch: it stops claiming chunks before it would need more
+
+// What a trim launch works on: the batch, the adapter pre-pass's answers, the outputs and where to run.  The kernel and its shape come from
+// trim_plan() (faqcs_trim_plan.h); each kernel file has one launcher that executes a plan (declared in faqcs_ctx.h).
+struct TrimArgs {
+    const uint8_t *seq, *qual;
+    const uint32_t *off;
+    uint32_t n_reads, max_len;
+    const uint32_t *ad_sl;
+    const uint16_t *ad_hit;
+    const uint8_t *tn_flags;
+    faqcs_read_result *out;
+    unsigned long long *rec_pre, *rec_post; // (trim_long writes no records: rec_pre is its scratch, a word per read for the terminal-N runs)
+    uint64_t *counters;
+    uint32_t *err;
+    int n_cu;
+    hipStream_t st;
+};
+inline TrimOptions trim_options(const DevParams &P) { return {P.mode, P.protect5, P.qc_only, P.replace_q, P.avgq_on, P.max_poly_n, P.dbg, P.has_adapters, P.trim5, P.trim3, P.fold_n}; }
 
 // base_tab fields (6 bits each so a lane can sum up to 63 reads before flushing)
 #define BT_SHIFT(code) (6 * (code))

@@ -1,5 +1,5 @@
 // faqcs_trim_common.h -- pieces shared by the trim kernels (faqcs_trim_kernel.hip, faqcs_trim_lds_kernel.hip):
-// the LDS accumulator layout (RowCfg), byte / bit helpers, the block flush and the per-chunk epilogue.
+// byte / bit helpers over the LDS accumulator layout (RowCfg, faqcs_trim_plan.h), the block flush and the per-chunk epilogue.
 #pragma once
 #include "faqcs_dev.h"
 
@@ -20,39 +20,6 @@ static inline hipError_t ensure_dynamic_lds(const void *kernel, size_t bytes, un
 }
 
 namespace {
-
-template <int C, int LPR, int WQ_ = 0> struct RowCfg {
-    static constexpr int D = (C + 3) / 4;          // dwords per lane per arena
-    static constexpr int W = LPR * C;              // positions covered by a row == columns of the LDS matrices
-    static constexpr int WQ = WQ_ ? WQ_ : W;       // columns of the position x quality matrix (trim_lds: a multiple of 32, see its Q-B pass)
-    // position x quality in LDS: one dword per cell (pre count lo16 / post count hi16) while that fits next to the
-    // other tables (W <= 768); wider rows pack two cells per dword as 8-bit pre/post counters and the block flushes
-    // them every 16 reads per wave (HQ8_EVERY x NW <= 255 increments per cell between flushes)
-    static constexpr bool HQ8 = W > 768;           // (768 wide: 158 KB of the CU's 160 KB LDS, one block per CU)
-    static constexpr int HQ8_EVERY = 16;
-    static constexpr int HQ = HQ8 ? FAQCS_NQ * W / 2 : FAQCS_NQ * WQ;
-    // |sum of (Q - q)| <= W * 168: key bias and the bit width of a position field inside the argmax keys
-    static constexpr int KEY_BIAS = LPR <= 16 ? (1 << 16) : (1 << 18);
-    static constexpr int PB = LPR <= 16 ? 9 : 11;
-    static constexpr int FK = 2 * W;               // "first position" keys are FK - p (0 == none)
-    static constexpr int HB = FAQCS_NBASE * W;
-    static constexpr int O_HQ = 0;
-    static constexpr int O_HB = O_HQ + HQ;
-    static constexpr int O_LEN = O_HB + HB;        // [W+1] lo16 pre / hi16 post
-    static constexpr int O_RQ = O_LEN + W + 2;     // [42]  lo16 pre / hi16 post
-    static constexpr int O_BQPRE = O_RQ + 42;      // [42]
-    static constexpr int O_BQPOST = O_BQPRE + 42;  // [42]
-    static constexpr int O_FS = O_BQPOST + 42;     // [32]
-    static constexpr int N_ZERO = O_FS + FS_SLOTS; // everything above is zero-initialised and flushed
-    static constexpr int O_TBASE = N_ZERO;         // [256] base table
-    static constexpr int O_TLC = O_TBASE + 256;    // [W+1]
-    static constexpr int O_TAVGQ = O_TLC + W + 1;  // [W+1]
-    static constexpr int O_TMAGIC = O_TAVGQ + W + 1;
-    static constexpr int BMW = D <= 4 ? 4 : 8;     // dwords per byte-mask row (one or two ds_read_b128)
-    static constexpr int O_TBM = (O_TMAGIC + W + 1 + 3) & ~3; // [C+2][BMW] byte masks "first vb bytes of the lane's dwords" (trim_lds: vb <= C + 1)
-    static constexpr int LDS_DWORDS = O_TBM + BMW * (C + 2);
-    static constexpr int JB = C > 16 ? 5 : 4;      // bits of a position index inside the lane-local argmax keys
-};
 
 template <int D> struct __attribute__((packed, aligned(1))) PackedBytes { uint32_t w[D]; };
 

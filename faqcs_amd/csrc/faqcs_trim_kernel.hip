@@ -1,13 +1,11 @@
-// faqcs_trim_kernel.hip -- trim_filter_accumulate, composition_histogram and the trim dispatcher (gfx950, wave64).
+// faqcs_trim_kernel.hip -- trim_filter_accumulate and composition_histogram (gfx950, wave64).
 //
 // Replaces trim_read() and its helpers (trim.cpp:225-551, :553-597, :629-885, :1191-1216) for every read
 // of a batch.  Two kernels live in this file: trim_filter_accumulate (the single-pass trim kernel) and composition_histogram
 // (folds the per-read composition records).  The trim kernels of the library share the accumulators, the flush and the per-chunk
-// epilogue (faqcs_trim_common.h); faqcs_launch_trim at the end of this file picks one per submission by the longest read of the batch:
-//   trim_lds (faqcs_trim_lds_kernel.hip)    1 ... 304 bases, every option set but --replace_to_N_q and the FAQCS_DBG ablation bits
-//   trim_filter_accumulate                  everything else up to 1 024 bases (--replace_to_N_q, FAQCS_DBG, 305 ... 1 024 bases, and
-//                                           what FAQCS_TRIM_LDS=0 / FAQCS_TRIM_LDS4=0 / FAQCS_TRIM_LDS16=0 take from trim_lds): described here
-//   trim_long (faqcs_trim_long_kernel.hip)  a batch that holds a read of more than 1 024 bases (FAQCS_TRIM_LONG=1: every batch)
+// epilogue (faqcs_trim_common.h).  Which of them takes a submission, and in which shape, is decided in one place, trim_plan()
+// (faqcs_trim_plan.h); faqcs_launch_trim_filter_accumulate at the end of this file executes a plan that names this kernel: whatever trim_lds
+// (1 ... 304 bases) and trim_long (a read of more than 1 024 bases) leave.
 //
 // Mapping (trim_filter_accumulate).  LPR lanes share one read and lane l of the group owns the C consecutive positions [l*C, l*C+C), fetched
 // with ONE unaligned global_load_dwordx{D} per arena; a wave takes chunks of 64 reads.
@@ -43,13 +41,6 @@
 // Float semantics of the reference are folded into integer lookup tables built on the host
 // (DevParams); the only float op left is the composition-bin multiply, an exact IEEE v_mul_f32.
 #include "faqcs_trim_common.h"
-
-#ifndef FAQCS_TRIM_NW
-#define FAQCS_TRIM_NW 4        /* waves per block (A/B on MI355X: 4 waves x 3 blocks/CU beat 8 x 1 by 9 %) */
-#endif
-#ifndef FAQCS_TRIM_MINWAVES
-#define FAQCS_TRIM_MINWAVES 3  /* __launch_bounds__ 2nd argument: waves per SIMD the register allocator must allow */
-#endif
 
 // WINDOWED: an adapter pre-pass or --5end/--3end can move the window off [0, len); when false (the headline
 // configuration) the prefix sum runs over all positions without per-position window tests.
@@ -702,101 +693,52 @@ __global__ __launch_bounds__(NT) void composition_histogram(const unsigned long 
 
 // ---- launch wrappers ---------------------------------------------------------------------------------------
 template <int C, int LPR, int NW, bool WINDOWED, bool GENERIC>
-static hipError_t launch_trim_t(const DevParams &P, const uint8_t *seq, const uint8_t *qual, const uint32_t *off,
-                                uint32_t n_reads, const uint32_t *ad_sl, const uint16_t *ad_hit, faqcs_read_result *out,
-                                unsigned long long *rec_pre, unsigned long long *rec_post, uint64_t *counters, uint32_t *err,
-                                int n_cu, hipStream_t st)
+static hipError_t launch_trim_t(const TrimPlan &plan, const DevParams &P, const TrimArgs &a)
 {
     constexpr size_t lds = (size_t)RowCfg<C, LPR>::LDS_DWORDS * 4;
     static unsigned long long attr_done = 0;
     auto kern = trim_filter_accumulate<C, LPR, NW, WINDOWED, GENERIC>;
+    if (plan.NW != NW) return hipErrorInvalidValue;
     if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds, attr_done); e != hipSuccess) return e;
-    const uint32_t chunks = (n_reads + 63) / 64;
-    int blocks_per_cu = (int)((160 * 1024) / lds);
-    // (variants whose per-position arrays do not fit 168 VGPRs run at 2 waves/SIMD rather than spill: the kernel is issue-bound)
-    constexpr int minwaves = (LPR == 8 || C > 10) ? 2 : (FAQCS_TRIM_MINWAVES > 2 ? FAQCS_TRIM_MINWAVES : 2);
-    const int by_waves = (4 * minwaves + NW - 1) / NW; // resident waves per CU the registers allow
-    if (blocks_per_cu > by_waves) blocks_per_cu = by_waves;
-    if (blocks_per_cu < 1) blocks_per_cu = 1;
-    uint32_t grid = (chunks + NW - 1) / NW;
-    const uint32_t cap = (uint32_t)(n_cu * blocks_per_cu);
-    if (grid > cap) grid = cap;
-    if (grid == 0) return hipSuccess;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, st, P, seq, qual, off, n_reads, ad_sl, ad_hit,
-                       reinterpret_cast<uint2 *>(out), rec_pre, rec_post, counters, err);
+    if (plan.grid == 0) return hipSuccess;
+    hipLaunchKernelGGL(kern, dim3(plan.grid), dim3(NW * 64), lds, a.st, P, a.seq, a.qual, a.off, a.n_reads, a.ad_sl, a.ad_hit,
+                       reinterpret_cast<uint2 *>(a.out), a.rec_pre, a.rec_post, a.counters, a.err);
     return hipGetLastError();
 }
 
-// the four (WINDOWED, GENERIC) variants of one <C, LPR, NW> shape
-template <int C, int LPR, int NW, class... Args>
-static hipError_t launch_trim_variant(const bool windowed, const bool generic, const Args &...args)
+using TrimLaunch = hipError_t (*)(const TrimPlan &, const DevParams &, const TrimArgs &);
+// the (WINDOWED, GENERIC) variants of one <C, LPR, NW> shape: all four, or (from 321 bases on) the superset variant, at 512 bases beside the
+// default-set one
+template <int C, int LPR, int NW, TrimVariants V = TRIM_VARIANTS_FOUR> static TrimLaunch trim_variant(const TrimPlan &plan)
 {
-    return windowed ? (generic ? launch_trim_t<C, LPR, NW, true, true>(args...) : launch_trim_t<C, LPR, NW, true, false>(args...))
-                    : (generic ? launch_trim_t<C, LPR, NW, false, true>(args...) : launch_trim_t<C, LPR, NW, false, false>(args...));
+    if constexpr (V == TRIM_VARIANTS_FOUR)
+        return plan.windowed ? (plan.ext ? launch_trim_t<C, LPR, NW, true, true> : launch_trim_t<C, LPR, NW, true, false>)
+                             : (plan.ext ? launch_trim_t<C, LPR, NW, false, true> : launch_trim_t<C, LPR, NW, false, false>);
+    if (plan.windowed && plan.ext) return launch_trim_t<C, LPR, NW, true, true>;
+    if constexpr (V == TRIM_VARIANTS_ALL_OR_NONE) if (!plan.windowed && !plan.ext) return launch_trim_t<C, LPR, NW, false, false>;
+    return nullptr;
 }
 
-hipError_t faqcs_launch_trim_long(const DevParams &P, const uint8_t *seq, const uint8_t *qual, const uint32_t *off, uint32_t n_reads,
-                                  const uint32_t *ad_sl, const uint16_t *ad_hit, faqcs_read_result *out, uint64_t *counters, uint32_t *err,
-                                  int n_cu, hipStream_t st, uint32_t *lead_trail, uint32_t max_len); // faqcs_trim_long_kernel.hip
-hipError_t faqcs_launch_trim_lds(const DevParams &P, const uint8_t *seq, const uint8_t *qual, const uint32_t *off,
-                                 uint32_t n_reads, uint32_t max_len, const uint32_t *ad_sl, const uint16_t *ad_hit,
-                                 faqcs_read_result *out, unsigned long long *rec_pre, unsigned long long *rec_post,
-                                 uint64_t *counters, uint32_t *err, int n_cu, hipStream_t st, const uint8_t *tn_flags);
-
-static thread_local const char *g_last_trim_kernel = "";
-const char *faqcs_last_trim_kernel() { return g_last_trim_kernel; }
-bool faqcs_trim_lds_tail_folded();
-static thread_local bool g_last_trim_folded = false;
-// the last faqcs_launch_trim() of this thread folded the composition records DevParams::fold_* named (a trim_lds variant with room for the table)
-bool faqcs_last_trim_folded() { return g_last_trim_folded; }
-
-hipError_t faqcs_launch_trim(const DevParams &P, const uint8_t *seq, const uint8_t *qual, const uint32_t *off,
-                             uint32_t n_reads, uint32_t max_len, const uint32_t *ad_sl, const uint16_t *ad_hit,
-                             faqcs_read_result *out, unsigned long long *rec_pre, unsigned long long *rec_post,
-                             uint64_t *counters, uint32_t *err, int n_cu, hipStream_t st, const uint8_t *tn_flags)
+// executes a plan of trim_plan() that names trim_filter_accumulate: one row of TRIM_TFA_SHAPES each
+hipError_t faqcs_launch_trim_filter_accumulate(const TrimPlan &plan, const DevParams &P, const TrimArgs &a)
 {
-    g_last_trim_folded = false;
-    {   // trim_long (faqcs_trim_long_kernel.hip): a batch that holds a read of more than 1 024 bases; FAQCS_TRIM_LONG=1 sends every batch there (tests)
-        const char *e_long = getenv("FAQCS_TRIM_LONG"); // (read per launch: the tests switch it inside one process)
-        const bool force_long = e_long && atoi(e_long) != 0;
-        if (max_len > FAQCS_FAST_READ_LENGTH || force_long) {
-            g_last_trim_kernel = "trim_long";
-            // (scratch: a word per read for the terminal-N runs; the composition record array is free, trim_long writes no records)
-            return faqcs_launch_trim_long(P, seq, qual, off, n_reads, ad_sl, ad_hit, out, counters, err, n_cu, st, reinterpret_cast<uint32_t *>(rec_pre), max_len);
-        }
-    }
-    {   // trim_lds (faqcs_trim_lds_kernel.hip): every byte from HBM once, through LDS; FAQCS_TRIM_LDS=0 switches it off
-        static const bool lds_on = [] { const char *e = getenv("FAQCS_TRIM_LDS"); return !e || atoi(e) != 0; }();
-        if (lds_on) {
-            const hipError_t e = faqcs_launch_trim_lds(P, seq, qual, off, n_reads, max_len, ad_sl, ad_hit, out, rec_pre, rec_post, counters, err, n_cu, st, tn_flags);
-            if (e != hipErrorNotSupported) { g_last_trim_kernel = "trim_lds"; g_last_trim_folded = e == hipSuccess && faqcs_trim_lds_tail_folded(); return e; }
-        }
-    }
-    g_last_trim_kernel = "trim_filter_accumulate";
-    const bool windowed = P.has_adapters || ((P.trim5 || P.trim3) && !P.qc_only);
-    const bool generic = !(P.mode == FAQCS_MODE_BWA_PLUS && !P.protect5 && !P.qc_only && P.replace_q == 0 && !P.avgq_on &&
-                           P.max_poly_n == 2 && P.dbg == 0);
-    // one table of "longest read of the batch" -> <C, LPR, NW>; beside each row the lengths that reach it and how.  The lengths trim_lds owns
-    // (1 ... 304) arrive here with --replace_to_N_q or a FAQCS_DBG bit (GENERIC only), with FAQCS_TRIM_LDS=0 (every option set; FAQCS_TRIM_LDS4=0:
-    // <= 76, FAQCS_TRIM_LDS16=0: 153 ... 304), and when a submission holds more chunks than trim_lds's blocks can take between two flushes.
     constexpr int NW = FAQCS_TRIM_NW;
-#define FAQCS_TRIM_ARGS P, seq, qual, off, n_reads, ad_sl, ad_hit, out, rec_pre, rec_post, counters, err, n_cu, st
-    if (max_len <= 64) return launch_trim_variant<16, 4, NW>(windowed, generic, FAQCS_TRIM_ARGS);   //   0 ... 64    4 lanes per read (2x50)
-    if (max_len <= 76) return launch_trim_variant<19, 4, NW>(windowed, generic, FAQCS_TRIM_ARGS);   //  65 ... 76    (2x75)
-    if (max_len <= 104) return launch_trim_variant<13, 8, NW>(windowed, generic, FAQCS_TRIM_ARGS);  //  77 ... 104   8 lanes per read (2x100)
-    if (max_len <= 128) return launch_trim_variant<16, 8, NW>(windowed, generic, FAQCS_TRIM_ARGS);  // 105 ... 128
-    if (max_len <= 152) return launch_trim_variant<19, 8, NW>(windowed, generic, FAQCS_TRIM_ARGS);  // 129 ... 152   (2x150: 152 position slots instead of 160)
-    if (max_len <= 160) return launch_trim_variant<20, 8, NW>(windowed, generic, FAQCS_TRIM_ARGS);  // 153 ... 160
-    if (max_len <= 208) return launch_trim_variant<13, 16, NW>(windowed, generic, FAQCS_TRIM_ARGS); // 161 ... 208   16 lanes per read
-    if (max_len <= 256) return launch_trim_variant<16, 16, NW>(windowed, generic, FAQCS_TRIM_ARGS); // 209 ... 256   (2x250)
-    if (max_len <= 320) return launch_trim_variant<10, 32, NW>(windowed, generic, FAQCS_TRIM_ARGS); // 257 ... 320   two reads per wave (MiSeq 2x300); 305 ... 320 with every option set
-    // longer reads, always here: one superset variant per width (the 512-base case keeps the default-set variant as well)
-    if (max_len <= 512) // 321 ... 512
-        return (windowed || generic) ? launch_trim_t<16, 32, NW, true, true>(FAQCS_TRIM_ARGS) : launch_trim_t<16, 32, NW, false, false>(FAQCS_TRIM_ARGS);
-    if (max_len <= 768) return launch_trim_t<12, 64, NW, true, true>(FAQCS_TRIM_ARGS);  // 513 ... 768   the whole wave on one read
-    if (max_len <= 1024) return launch_trim_t<16, 64, 8, true, true>(FAQCS_TRIM_ARGS);  // 769 ... 1 024 (8 waves x 16 reads <= 255 per 8-bit cell)
-#undef FAQCS_TRIM_ARGS
-    return hipErrorInvalidValue;
+    TrimLaunch f = nullptr;
+    switch (trim_shape_key(plan.C, plan.LPR)) {
+    case trim_shape_key(16, 4): f = trim_variant<16, 4, NW>(plan); break;
+    case trim_shape_key(19, 4): f = trim_variant<19, 4, NW>(plan); break;
+    case trim_shape_key(13, 8): f = trim_variant<13, 8, NW>(plan); break;
+    case trim_shape_key(16, 8): f = trim_variant<16, 8, NW>(plan); break;
+    case trim_shape_key(19, 8): f = trim_variant<19, 8, NW>(plan); break;
+    case trim_shape_key(20, 8): f = trim_variant<20, 8, NW>(plan); break;
+    case trim_shape_key(13, 16): f = trim_variant<13, 16, NW>(plan); break;
+    case trim_shape_key(16, 16): f = trim_variant<16, 16, NW>(plan); break;
+    case trim_shape_key(10, 32): f = trim_variant<10, 32, NW>(plan); break;
+    case trim_shape_key(16, 32): f = trim_variant<16, 32, NW, TRIM_VARIANTS_ALL_OR_NONE>(plan); break;
+    case trim_shape_key(12, 64): f = trim_variant<12, 64, NW, TRIM_VARIANTS_ALL>(plan); break;
+    case trim_shape_key(16, 64): f = trim_variant<16, 64, 8, TRIM_VARIANTS_ALL>(plan); break;
+    }
+    return f ? f(plan, P, a) : hipErrorInvalidValue; // (a shape or variant this file does not compile: a programming error)
 }
 
 // wide: the two-word records of the long-read kernels (max_len > 256).  One launch for the pre- and the post-trim records.

@@ -61,8 +61,8 @@
 // tests/test_gpu_slot_rule.py runs batches of every lane geometry through a build that counts the adds outside the matrix
 // (-DFAQCS_LDS_DIAG_CHECK_QB_ADDR, built by __graft_entry__.build() as tests/_diag/libfaqcs_mi_qbchk.so): the count must be zero.
 //
-// Dispatch (faqcs_launch_trim_lds at the end of the file): every option set except --replace_to_N_q.  A chunk whose reads all have the
-// same length, a multiple of 32 bases, is staged as padded rows instead of one span (dma_rows: LDS bank stride of the lane-per-read passes).
+// Dispatch: trim_plan() (faqcs_trim_plan.h) names the shape, faqcs_launch_trim_lds at the end of the file executes it: every option set
+// except --replace_to_N_q.  A chunk whose reads all have the same length, a multiple of 32 bases, is staged as padded rows instead of one span (dma_rows: LDS bank stride of the lane-per-read passes).
 #include "faqcs_trim_common.h"
 
 #include <stdlib.h>
@@ -72,61 +72,11 @@
 #ifndef FAQCS_LDS_SUM_UNROLL
 #define FAQCS_LDS_SUM_UNROLL 4
 #endif
-// reads per chunk of the 16-lanes-per-read variants (A/B on MI355X: see faqcs_launch_trim_lds)
-#ifndef FAQCS_LDS16_RPC
-#define FAQCS_LDS16_RPC 32
-#endif
-#ifndef FAQCS_LDS16_NW
-#define FAQCS_LDS16_NW 12
-#endif
 #ifndef FAQCS_LDS_SA_UNROLL
 #define FAQCS_LDS_SA_UNROLL 2
 #endif
 
 namespace {
-
-// Q-B's own partition of the positions (8 lanes per read, C = 19): 20 per lane instead of 19, quality rows of 160 cells.  With rows that are a
-// multiple of 32 cells the bank of a cell is its position mod 32 whatever the quality; lane rl of a read starts at position 20 rl
-// (banks 0, 20, 8, 28, 16, 4, 24, 12: the multiples of 4) and the four reads of a half wave walk their 20 positions ROTATED by
-// 0, 1, 2, 3 bytes, so the 32 lanes of one ds_add hit 32 different banks -- and four different positions: no two adds of an
-// instruction meet on a bank or on a cell (the round-2 kernel lost half of its LDS-atomic time to such conflicts).
-// 16 lanes per read (C = 16, reads of 161 ... 252 bases): a lane's 16 cells are followed by one cell of padding, so lane rl starts on
-// cell 17 rl -- 16 different banks in rows of 288 cells -- and the two reads of a half wave are rotated by 0 and 1 bytes
-// (17 rl + 1 = 17 rl' has no solution with both lanes below 16): conflict-free as well.
-// 16 lanes per read, C = 19 (reads of 253 ... 304 bases: 2x300): 20 positions per lane in Q-B as in the 8-lane variant, 21 cells per lane, rows of 352.
-constexpr int lds_cq(int C, int LPR = 8) { return C == 19 ? 20 : C; }
-constexpr int lds_qstride(int C, int LPR = 8) { return LPR == 16 ? lds_cq(C, LPR) + 1 : lds_cq(C, LPR); } // cells from one lane's first position to the next lane's
-constexpr int lds_wq(int C, int LPR = 8) { return (LPR == 16 || C == 19) ? (LPR * lds_qstride(C, LPR) + 31) / 32 * 32 : 0; } // (8 lanes, C = 19: 160; 4 lanes: 96)
-constexpr int lds_nrot(int C, int LPR = 8) { return LPR == 16 ? 2 : (C == 19 ? 4 : 1); }   // reads of a half wave = byte rotations in use
-// The longest read a variant takes.  Up to 252 bases the step index of a walk lives in the low byte of the argmax keys (codes 254 - step), a
-// window's start and length in a byte each, a read's N count in 8 bits; the 304-base variant (lds_wide) has nine-bit codes and fields, the
-// N counts in a register of their own and two-word composition records.
-constexpr int lds_maxlen(int C, int LPR = 8) { return LPR * C <= 252 ? LPR * C : (LPR * C == 256 ? 252 : LPR * C); }
-constexpr bool lds_wide(int C, int LPR = 8) { return lds_maxlen(C, LPR) > 252; }
-
-template <int C, int NW, int LPR = 8, int RPC = 64> struct LdsCfg {
-    using Row = RowCfg<C, LPR, lds_wq(C, LPR)>;
-    static constexpr int CQ = lds_cq(C, LPR);                  // positions per lane in Q-B
-    static constexpr int QSTRIDE = lds_qstride(C, LPR);        // cells per lane in a quality row
-    static constexpr int NROT = lds_nrot(C, LPR);
-    static constexpr bool ROT = NROT > 1;
-    static constexpr int W = Row::W;
-    static constexpr int MAXLEN = lds_maxlen(C, LPR);
-    static constexpr int ND = (W + 3) / 4;                     // dwords of the longest read
-    static constexpr int NP = (W + 15) / 16;                   // 16-byte pieces (the out-of-line exact passes)
-    static constexpr int NWORD = (ND * 4 + 31) / 32;
-    static constexpr int O_T2 = (Row::LDS_DWORDS + 3) & ~3;    // [256][2] (exact passes of rare reads) A,T,C,G one-hot in 8-bit fields ; isN(upper) | isN(any) << 1
-    static constexpr int O_T3 = O_T2 + 512;                    // [256][2] S: 6-bit count fields, pre ; post (entry[b | 0x80]: b outside the kept window, pre only)
-    static constexpr int O_CTR = O_T3 + 512;                   // [8] the block's chunk queue: [0] next unclaimed chunk number, [1] the block's chunk
-                                                               // count once known, [4..7] ring: group number << 20 | group id
-    static constexpr int O_TBQ = O_CTR + 8;                    // (ROT) [NROT][CQ + 1][8] rotated byte masks "positions < vb" of Q-B
-    static constexpr int O_STG = O_TBQ + (ROT ? NROT * (CQ + 1) * 8 : 0);
-    static constexpr int PADLEN = MAXLEN / 32 * 32;            // the longest read of a chunk staged as padded rows (dma_rows): L + 16 bytes each
-    static constexpr int STG_BYTES = RPC * (PADLEN + 16 > MAXLEN ? PADLEN + 16 : MAXLEN) + 32; // one arena's span of a chunk (RPC reads) + 16-byte alignment slack
-    static constexpr int STG_DW = (STG_BYTES + 15) / 16 * 4;
-    static constexpr int TAIL_PAD = W + 64 > 256 ? (W + 64) / 4 : 64; // dwords: a lane may read W + 20 bytes from the start of the span's last read
-    static constexpr int lds_dwords() { return O_STG + NW * STG_DW + TAIL_PAD; }
-};
 
 typedef uint32_t LdsPair2 __attribute__((ext_vector_type(2)));
 typedef const __attribute__((address_space(3))) LdsPair2 *lds_u2c_ptr;
@@ -320,9 +270,6 @@ __device__ __noinline__ ExactB exact_bases(const uint8_t *__restrict__ seq, cons
 
 } // namespace
 
-// waves per block = slots of 64 x MAXLEN bytes next to the accumulators in 160 KB: 12 x 9.8 KB + 37 KB (8 lanes per read), 6 x 16.2 KB + 63 KB (16)
-constexpr int lds_waves(int C, int LPR = 8, int RPC = 64) { return LPR == 4 ? 12 : LPR == 16 ? (RPC == 64 ? 6 : (C == 19 ? 12 : FAQCS_LDS16_NW)) : (C <= 19 ? 12 : 8); }
-
 // LDS accumulators -> a row of global memory that belongs to THIS block and THIS flush, as plain coalesced 16-byte stores of the
 // cells as they are (pre count in the low, post count in the high half-word); fold_partials, launched behind the trim kernel, adds
 // the rows of all blocks to the u64 counter block.  History: the direct flush of faqcs_trim_common.h costs one 64-bit global atomic
@@ -412,9 +359,6 @@ __global__ __launch_bounds__(1024) void fold_partials(const uint32_t *__restrict
 // RPC = reads per chunk: 64 (one per lane in the lane-per-read passes) or 32 -- half the lanes idle there, but a slot of half the size: reads of
 // 161 ... 252 bases get 12 waves per CU instead of 6.  The position-parallel passes run TPR = RPC x LPR / 64 steps per chunk; the lane that owns a
 // read in the lane-per-read passes is lane t of the row of LPR lanes that works on it in step t.
-// a variant whose block owns at least the 122 KB the composition fold needs (the table of 16-bit counters, the per-length factors)
-template <int C, int NW, int LPR, int RPC> constexpr bool lds_tail_folds_v =
-    LdsCfg<C, NW, LPR, RPC>::lds_dwords() >= (FAQCS_NCOMP_BIN * FAQCS_NCOMP_KIND + 1) / 2 + 512 + 8 && lds_maxlen(C, LPR) <= 256; // (one-word records)
 template <int C, int NW, bool WINDOWED, bool EXT, int LPR, int RPC>
 __global__ __launch_bounds__(NW * 64, NW / 4) void trim_lds(
     const DevParams P, const uint8_t *__restrict__ seq, const uint8_t *__restrict__ qual,
@@ -521,11 +465,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void trim_lds(
     // flush k (k = 1, 2, ...) comes before the block's chunk k * FLUSH_CHUNKS, the last one after its last chunk: the 16-bit halves of
     // the LDS cells take FLUSH_CHUNKS x 64 <= 65535 increments in between (chunks are claimed in order, so a wave that holds a chunk
     // >= k * FLUSH_CHUNKS waits at flush k while exactly the chunks below it are being finished)
-#ifdef FAQCS_LDS_TEST_FLUSH_CHUNKS // (test build: flush every few chunks, so that a small launch goes through many flushes and fills every block's rows)
-    constexpr uint32_t FLUSH_CHUNKS = (uint32_t)(FAQCS_LDS_TEST_FLUSH_CHUNKS) / NW * NW;
-#else
-    constexpr uint32_t FLUSH_CHUNKS = 65535u / RPC / NW * NW;
-#endif
+    constexpr uint32_t FLUSH_CHUNKS = lds_flush_chunks(NW, RPC);
     constexpr uint32_t MAX_GROUPS = (uint32_t)FAQCS_PARTIAL_FLUSHES * FLUSH_CHUNKS / NW; // groups a block takes at most: one flush row per FLUSH_CHUNKS chunks
     constexpr uint32_t REG_FLUSH_EVERY = 63 / TPR; // 6-bit fields: 7 chunks x 8 reads (3 x 16) per row <= 63
     constexpr uint32_t NO_CHUNK = 0xffffffffu;
@@ -896,7 +836,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void trim_lds(
         c_next = uniu(c_next);
         // the first chunk of group number L: ask for the id of group number L + 1 (published below, behind this chunk's loads)
         // (a block has FAQCS_PARTIAL_FLUSHES rows to flush into: before it would need another one it stops asking for groups, and the
-        // blocks that have room take what is left -- faqcs_launch_trim_lds makes sure they have)
+        // blocks that have room take what is left -- trim_plan() makes sure they have)
         const bool at_group_start = c_next % NW == 0 && c_next < lds_word(1);
         const bool fetch_group = at_group_start && c_next / NW + 1u < MAX_GROUPS;
         uint32_t g_new = 0;
@@ -1588,77 +1528,42 @@ hipError_t faqcs_launch_terminal_n_flags(const uint8_t *seq, const uint32_t *off
     return hipGetLastError();
 }
 
-static thread_local bool g_trim_lds_tail_folded = false;
-bool faqcs_trim_lds_tail_folded() { return g_trim_lds_tail_folded; }
 template <int C, bool WINDOWED, bool EXT, int LPR = 8, int RPC = 64>
-static hipError_t launch_trim_lds(const DevParams &P, const uint8_t *seq, const uint8_t *qual, const uint32_t *off,
-                                  uint32_t n_reads, const uint32_t *ad_sl, const uint16_t *ad_hit, faqcs_read_result *out,
-                                  unsigned long long *rec_pre, unsigned long long *rec_post, uint64_t *counters, uint32_t *err,
-                                  int n_cu, hipStream_t st, const uint8_t *tn_flags)
+static hipError_t launch_trim_lds(const TrimPlan &plan, const DevParams &P, const TrimArgs &a)
 {
     constexpr int NW = lds_waves(C, LPR, RPC);
     constexpr size_t lds = (size_t)LdsCfg<C, NW, LPR, RPC>::lds_dwords() * 4;
     static unsigned long long attr_done = 0;
     auto kern = trim_lds<C, NW, WINDOWED, EXT, LPR, RPC>;
+    if (plan.NW != NW || plan.RPC != RPC) return hipErrorInvalidValue;
     if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds, attr_done); e != hipSuccess) return e;
-    const uint32_t chunks = (n_reads + RPC - 1) / RPC;
-    uint32_t grid = (chunks + NW - 1) / NW;
-    if (grid > (uint32_t)n_cu) grid = (uint32_t)n_cu; // one block per CU: its LDS holds a slot per wave
-    if (grid == 0) return hipSuccess;
-    // every block can take FAQCS_PARTIAL_FLUSHES x 1020 chunks: a launch the blocks could not take between them goes to another kernel
-#ifdef FAQCS_LDS_TEST_FLUSH_CHUNKS
-    if ((uint64_t)chunks > (uint64_t)grid * FAQCS_PARTIAL_FLUSHES * ((uint32_t)(FAQCS_LDS_TEST_FLUSH_CHUNKS) / NW * NW)) return hipErrorNotSupported; // (up to the brim)
-#else
-    if ((uint64_t)chunks > (uint64_t)grid * FAQCS_PARTIAL_FLUSHES * (65535u / RPC / NW * NW) * 3 / 4) return hipErrorNotSupported;
-#endif
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, st, P, seq, qual, off, n_reads, ad_sl, ad_hit,
-                       reinterpret_cast<uint2 *>(out), rec_pre, rec_post, counters, err, tn_flags);
+    if (plan.grid == 0) return hipSuccess;
+    hipLaunchKernelGGL(kern, dim3(plan.grid), dim3(NW * 64), lds, a.st, P, a.seq, a.qual, a.off, a.n_reads, a.ad_sl, a.ad_hit,
+                       reinterpret_cast<uint2 *>(a.out), a.rec_pre, a.rec_post, a.counters, a.err, a.tn_flags);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    g_trim_lds_tail_folded = lds_tail_folds_v<C, NW, LPR, RPC> && P.fold_n != 0; // (the launch folds the composition records P.fold_* names, all of them)
-    hipLaunchKernelGGL((fold_partials<C, LPR>), dim3((RowCfg<C, LPR, lds_wq(C, LPR)>::N_ZERO + 63) / 64), dim3(1024), 0, st, P.partials, P.partial_rows, grid, counters, P.lay, err + 8);
+    hipLaunchKernelGGL((fold_partials<C, LPR>), dim3((RowCfg<C, LPR, lds_wq(C, LPR)>::N_ZERO + 63) / 64), dim3(1024), 0, a.st, P.partials, P.partial_rows, plan.grid, a.counters, P.lay, a.err + 8);
     return hipGetLastError();
 }
 
+using TrimLaunch = hipError_t (*)(const TrimPlan &, const DevParams &, const TrimArgs &);
 // the four (WINDOWED, EXT) variants of one <C, LPR, RPC> shape
-template <int C, int LPR, int RPC, class... Args>
-static hipError_t launch_trim_lds_variant(const bool windowed, const bool ext, const Args &...args)
+template <int C, int LPR, int RPC> static TrimLaunch trim_lds_variant(const TrimPlan &plan)
 {
-    return ext ? (windowed ? launch_trim_lds<C, true, true, LPR, RPC>(args...) : launch_trim_lds<C, false, true, LPR, RPC>(args...))
-               : (windowed ? launch_trim_lds<C, true, false, LPR, RPC>(args...) : launch_trim_lds<C, false, false, LPR, RPC>(args...));
+    return plan.ext ? (plan.windowed ? launch_trim_lds<C, true, true, LPR, RPC> : launch_trim_lds<C, false, true, LPR, RPC>)
+                    : (plan.windowed ? launch_trim_lds<C, true, false, LPR, RPC> : launch_trim_lds<C, false, false, LPR, RPC>);
 }
 
-// Returns hipErrorNotSupported when the configuration is not one trim_lds is compiled for (the caller then takes the
-// other trim kernels).
-hipError_t faqcs_launch_trim_lds(const DevParams &P, const uint8_t *seq, const uint8_t *qual, const uint32_t *off,
-                                 uint32_t n_reads, uint32_t max_len, const uint32_t *ad_sl, const uint16_t *ad_hit,
-                                 faqcs_read_result *out, unsigned long long *rec_pre, unsigned long long *rec_post,
-                                 uint64_t *counters, uint32_t *err, int n_cu, hipStream_t st, const uint8_t *tn_flags)
+// executes a plan of trim_plan() that names trim_lds: one row of TRIM_LDS_SHAPES each
+hipError_t faqcs_launch_trim_lds(const TrimPlan &plan, const DevParams &P, const TrimArgs &a)
 {
-    g_trim_lds_tail_folded = false;
-    const bool windowed = P.has_adapters || ((P.trim5 || P.trim3) && !P.qc_only);
-    const bool plain = P.mode == FAQCS_MODE_BWA_PLUS && !P.protect5 && !P.qc_only && P.replace_q == 0 && !P.avgq_on &&
-                       P.max_poly_n == 2 && P.dbg == 0;
-    // every option set except --replace_to_N_q (its G -> N edit needs base and quality of a position together) and the ablation bits
-    const bool ext = !plain && P.replace_q == 0 && P.dbg == 0;
-    if (!plain && !ext) return hipErrorNotSupported;
-    // 253 ... 304 bases: the composition records are the two-word ones when the batch holds a read past 256 bases
-    DevParams Pw = P;
-    Pw.wide_records = max_len > 256 ? 1u : 0u;
-    // FAQCS_TRIM_LDS4=0 leaves reads of up to 76 bases to trim_filter_accumulate, FAQCS_TRIM_LDS16=0 those of 153 ... 304 (A/B runs)
-    static const bool lds4_on = [] { const char *e = getenv("FAQCS_TRIM_LDS4"); return !e || atoi(e) != 0; }();
-    static const bool lds16_on = [] { const char *e = getenv("FAQCS_TRIM_LDS16"); return !e || atoi(e) != 0; }();
-    // longest read of the batch -> <C, LPR, RPC>.  C = 19 takes 2x125 as well: C = 16's 128-dword rows put every read of a half wave on the same
-    // banks (4.44 against 5.64 G reads/s).  From 153 bases on: 16 lanes per read with smaller chunks; equal-length chunks of a multiple of 32 bases
-    // are staged as padded rows (every lane of a lane-per-read pass would meet on one LDS bank otherwise).  The measurements behind this table:
-    // DESIGN_HISTORY.md.
-    constexpr uint32_t L16 = lds_maxlen(16, 16), L19 = lds_maxlen(19, 16); // 252, 304
-#define FAQCS_LDS_ARGS(P) windowed, ext, P, seq, qual, off, n_reads, ad_sl, ad_hit, out, rec_pre, rec_post, counters, err, n_cu, st, tn_flags
-    if (lds4_on && max_len > 0 && max_len <= 52) return launch_trim_lds_variant<13, 4, 64>(FAQCS_LDS_ARGS(P));   //   1 ... 52    4 lanes per read: sixteen reads per step of the position-parallel passes (2x50)
-    if (lds4_on && max_len > 52 && max_len <= 76) return launch_trim_lds_variant<19, 4, 64>(FAQCS_LDS_ARGS(P));  //  53 ... 76    (2x75)
-    if (max_len > 76 && max_len <= 104) return launch_trim_lds_variant<13, 8, 64>(FAQCS_LDS_ARGS(P));            //  77 ... 104   8 lanes per read (2x100)
-    if (max_len > 104 && max_len <= 152) return launch_trim_lds_variant<19, 8, 64>(FAQCS_LDS_ARGS(P));           // 105 ... 152   (2x125, 2x150)
-    if (lds16_on && max_len > 152 && max_len <= L16) return launch_trim_lds_variant<16, 16, FAQCS_LDS16_RPC>(FAQCS_LDS_ARGS(P)); // 153 ... 252   16 lanes per read (2x250, 2x251)
-    if (lds16_on && max_len > L16 && max_len <= L19) return launch_trim_lds_variant<19, 16, 20>(FAQCS_LDS_ARGS(Pw)); // 253 ... 304   16 lanes x 19 positions, chunks of 20 reads (2x300, 2x301: 6 KB slots, 12 waves beside a [42][352] quality matrix)
-#undef FAQCS_LDS_ARGS
-    return hipErrorNotSupported;
+    TrimLaunch f = nullptr;
+    switch (trim_shape_key(plan.C, plan.LPR)) {
+    case trim_shape_key(13, 4): f = trim_lds_variant<13, 4, 64>(plan); break;
+    case trim_shape_key(19, 4): f = trim_lds_variant<19, 4, 64>(plan); break;
+    case trim_shape_key(13, 8): f = trim_lds_variant<13, 8, 64>(plan); break;
+    case trim_shape_key(19, 8): f = trim_lds_variant<19, 8, 64>(plan); break;
+    case trim_shape_key(16, 16): f = trim_lds_variant<16, 16, FAQCS_LDS16_RPC>(plan); break;
+    case trim_shape_key(19, 16): f = trim_lds_variant<19, 16, 20>(plan); break;
+    }
+    return f ? f(plan, P, a) : hipErrorInvalidValue; // (a shape this file does not compile: a programming error)
 }

@@ -526,21 +526,19 @@ __global__ __launch_bounds__(LA_NW * 64) void long_accumulate(const DevParams P,
     }
 }
 
-hipError_t faqcs_launch_trim_long(const DevParams &P, const uint8_t *seq, const uint8_t *qual, const uint32_t *off, uint32_t n_reads,
-                                  const uint32_t *ad_sl, const uint16_t *ad_hit, faqcs_read_result *out, uint64_t *counters, uint32_t *err,
-                                  int n_cu, hipStream_t st, uint32_t *lead_trail, uint32_t max_len)
+// executes a plan of trim_plan() that names trim_long
+hipError_t faqcs_launch_trim_long(const TrimPlan &plan, const DevParams &P, const TrimArgs &a)
 {
-    if (n_reads == 0) return hipSuccess;
-    constexpr int NW = 4;
-    uint32_t grid = (n_reads + NW - 1) / NW;
-    const uint32_t cap = (uint32_t)n_cu * 8u; // 32 waves per CU: the passes wait on memory, not on issue slots
-    if (grid > cap) grid = cap;
-    hipLaunchKernelGGL((trim_long<NW>), dim3(grid), dim3(NW * 64), 0, st, P, seq, qual, off, n_reads, ad_sl, ad_hit,
-                       reinterpret_cast<uint2 *>(out), counters, err, lead_trail);
+    constexpr int NW = FAQCS_TRIM_LONG_NW;
+    if (plan.NW != NW) return hipErrorInvalidValue;
+    if (a.n_reads == 0) return hipSuccess;
+    uint32_t *lead_trail = reinterpret_cast<uint32_t *>(a.rec_pre); // (scratch: a word per read for the terminal-N runs; the record array is free)
+    hipLaunchKernelGGL((trim_long<NW>), dim3(plan.grid), dim3(NW * 64), 0, a.st, P, a.seq, a.qual, a.off, a.n_reads, a.ad_sl, a.ad_hit,
+                       reinterpret_cast<uint2 *>(a.out), a.counters, a.err, lead_trail);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    uint32_t g2 = (n_reads + LA_NW - 1) / LA_NW;
-    if (g2 > (uint32_t)n_cu) g2 = (uint32_t)n_cu; // one block per CU (its 94 KB of LDS)
-    hipLaunchKernelGGL(long_accumulate, dim3(g2), dim3(LA_NW * 64), 0, st, P, seq, qual, off, n_reads, reinterpret_cast<const uint2 *>(out), lead_trail,
-                       counters, max_len);
+    uint32_t g2 = (a.n_reads + LA_NW - 1) / LA_NW;
+    if (g2 > (uint32_t)a.n_cu) g2 = (uint32_t)a.n_cu; // one block per CU (its 94 KB of LDS)
+    hipLaunchKernelGGL(long_accumulate, dim3(g2), dim3(LA_NW * 64), 0, a.st, P, a.seq, a.qual, a.off, a.n_reads, reinterpret_cast<const uint2 *>(a.out), lead_trail,
+                       a.counters, a.max_len);
     return hipGetLastError();
 }

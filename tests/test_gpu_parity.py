@@ -8,6 +8,7 @@ import pytest
 
 from faqcs_amd import _capi as capi
 from faqcs_amd.options import parse_args
+from trim_dispatch_cases import DISPATCH_ROWS
 
 pytestmark = pytest.mark.gpu
 
@@ -1814,16 +1815,7 @@ def test_take_back_pass_under_load(L):
     compare_engines(opt, reads, seg_size=4000)
 
 
-@pytest.mark.parametrize("L,args,kernel", [
-    (150, [], "trim_lds"), (151, ["--adapter"], "trim_lds"), (100, ["--mode", "HARD", "-q", "10"], "trim_lds"), (125, ["--qc_only"], "trim_lds"),
-    (128, [], "trim_lds"), (96, [], "trim_lds"), (75, [], "trim_lds"), (160, [], "trim_lds"), (157, ["--5trim_off"], "trim_lds"), (64, [], "trim_lds"), (50, ["--adapter"], "trim_lds"), (36, ["--mode", "BWA"], "trim_lds"),
-    (75, ["--replace_to_N_q", "15"], "trim_filter_accumulate"),
-    (150, ["--replace_to_N_q", "15"], "trim_filter_accumulate"), (128, ["--qc_only"], "trim_lds"), (192, ["--adapter"], "trim_lds"),
-    (250, [], "trim_lds"), (251, ["--adapter", "--polyA"], "trim_lds"), (200, ["--mode", "BWA", "--avg_q", "20"], "trim_lds"), (161, [], "trim_lds"), (252, [], "trim_lds"),
-    (253, [], "trim_lds"), (224, [], "trim_lds"), (256, [], "trim_lds"), (250, ["--replace_to_N_q", "15"], "trim_filter_accumulate"),
-    (300, [], "trim_lds"), (301, ["--adapter", "--polyA"], "trim_lds"), (304, ["--mode", "HARD", "-q", "10"], "trim_lds"), (305, [], "trim_filter_accumulate"),
-    (300, ["--replace_to_N_q", "15"], "trim_filter_accumulate"),
-])
+@pytest.mark.parametrize("L,args,kernel", DISPATCH_ROWS)  # (tests/test_trim_plan.py holds trim_plan() to the same rows without a GPU)
 def test_dispatcher_picks_the_documented_trim_kernel(L, args, kernel):
     """DESIGN.md section 4 names the trim kernel of every (read length, option set) class; faqcs_kernel_report() says which one ran."""
     import ctypes as C
@@ -1835,6 +1827,32 @@ def test_dispatcher_picks_the_documented_trim_kernel(L, args, kernel):
     kt = capi.KernelTimes()
     assert hip.lib.faqcs_kernel_report(hip.ctx, C.byref(kt)) == 0
     assert (kt.trim_kernel or b"").decode() == kernel
+
+
+def test_one_context_through_every_kind_of_trim_plan():
+    """Submissions of 300 reads on ONE context whose longest reads have 150, 300, 305, 1 100 and 150 bases, and 150 once more: trim_lds with
+    one-word records, trim_lds with two-word records, trim_filter_accumulate, trim_long and back.  Each launch folds -- or leaves to
+    composition_histogram -- the records of the one before it (faqcs_ctx::pending_fold, pending_wide): the second fold is of one-word records
+    beside a launch that writes two-word ones, the next two of two-word records, trim_long leaves none and keeps its scratch in a record array,
+    and the last launch (the sixth submission is there for it) folds the fifth's records in its blocks' tails.  The kernel after every submission,
+    and the whole counter block at the end against the oracle's."""
+    import ctypes as C
+
+    from oracle_engine import OracleEngine
+
+    from faqcs_amd import driver
+
+    opt = parse_args(["-u", "x", "-d", "y"])
+    rng = np.random.Generator(np.random.PCG64([6, SEED]))
+    hip, ora = hip_factory(opt, 2048, 33), OracleEngine(opt, 2048, 33)
+    for L, kernel in [(150, "trim_lds"), (300, "trim_lds"), (305, "trim_filter_accumulate"), (1100, "trim_long"), (150, "trim_lds"), (150, "trim_lds")]:
+        reads = random_batch(rng, 299, L, "ragged") + [(b"@x", make_uniform(rng, L), bytes((rng.integers(20, 41, L) + 33).astype(np.uint8)))]
+        seq, qual, offset, seg = driver.pack_segments([reads])
+        assert (hip.process(seq, qual, offset, seg) == ora.process(seq, qual, offset, seg)).all()
+        kt = capi.KernelTimes()
+        assert hip.lib.faqcs_kernel_report(hip.ctx, C.byref(kt)) == 0
+        assert (kt.trim_kernel or b"").decode() == kernel
+    assert (hip.counters() == ora.counters()).all()
 
 
 def make_uniform(rng, L):
