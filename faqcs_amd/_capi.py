@@ -77,6 +77,23 @@ class RenderOut(C.Structure):
     _fields_ = [("text", C.c_void_p), ("capacity_bytes", C.c_uint64), ("rec_offset", C.c_void_p), ("rec_index", C.c_void_p), ("info", C.c_void_p)]
 
 
+class Mate(C.Structure):
+    """faqcs_mate: one mate's buffer as faqcs_parse_device + faqcs_submit_device left it.  `batch` points to a Batch in host memory (keep it
+    alive); the other pointers are device pointers for the device forms, host pointers for the host forms."""
+    _fields_ = [("batch", C.POINTER(Batch)), ("results", C.c_void_p), ("text", C.c_void_p), ("def_pos", C.c_void_p), ("def_len", C.c_void_p)]
+
+
+class PairInfo(C.Structure):
+    """faqcs_pair_info: the pairs routed, the first pair whose ids differ, and the two FilterStat slots that depend on both mates."""
+    _fields_ = [("paired_read_number", C.c_uint64), ("paired_base_length", C.c_uint64), ("n_pairs", C.c_uint32), ("mismatch", C.c_uint32),
+                ("id_len", C.c_uint32 * 2), ("n_one_valid", C.c_uint32), ("n_none_valid", C.c_uint32)]
+
+
+ROUTE_V1, ROUTE_V2, ROUTE_NOWHERE = 1, 2, 0x80
+FILE_QC1, FILE_QC2, FILE_UNPAIRED, FILE_DISCARD = range(4)
+# the reference's names of the four files of a paired run, by FAQCS_FILE_* code
+PAIR_FILES = ("QC.1.trimmed.fastq", "QC.2.trimmed.fastq", "QC.unpaired.trimmed.fastq", "QC.discard.trimmed.fastq")
+
 # FAQCS_INFLATE_*: faqcs_inflate_info.error / faqcs_bgzf_index_info.error, the error of member n_members
 INFLATE_OK, INFLATE_E_HEADER, INFLATE_E_LENGTH, INFLATE_E_DATA, INFLATE_E_CRC, INFLATE_E_TRUNCATED = range(6)
 
@@ -220,6 +237,12 @@ def load_library():
         "faqcs_render_device": (i32, [vp, C.POINTER(Batch), vp, vp, vp, vp, vp, vp, C.POINTER(RenderOut)]),
         "faqcs_render_host": (i32, [C.POINTER(Params), C.POINTER(Batch), vp, vp, vp, vp, vp, vp, C.POINTER(RenderOut)]),
         "faqcs_render_time_ms": (i32, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+        "faqcs_pair_device": (i32, [vp, C.POINTER(Mate), C.POINTER(Mate), vp, vp]),
+        "faqcs_pair_host": (i32, [C.POINTER(Mate), C.POINTER(Mate), vp, vp]),
+        "faqcs_pair_time_ms": (i32, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+        "faqcs_render_pair_device": (i32, [vp, i32, C.POINTER(Mate), C.POINTER(Mate), vp, u32, C.POINTER(RenderOut)]),
+        "faqcs_render_pair_host": (i32, [C.POINTER(Params), i32, C.POINTER(Mate), C.POINTER(Mate), vp, u32, C.POINTER(RenderOut)]),
+        "faqcs_render_pair_time_ms": (i32, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "faqcs_inflate_error_text": (C.c_char_p, [i32]),
         "faqcs_bgzf_index_host": (i32, [vp, u64, i32, vp, u32, C.POINTER(BgzfIndexInfo)]),
         "faqcs_inflate_device": (i32, [vp, vp, u64, vp, u32, C.POINTER(InflateOut)]),

@@ -1,5 +1,5 @@
 // faqcs_capi_seam.hip -- the device seams of the C ABI (include/faqcs_mi.h): faqcs_emit_device, faqcs_parse_device, faqcs_render_device,
-// faqcs_inflate_device and faqcs_deflate_device with their faqcs_*_time_ms.  Each is two stages of kernels between the marks of a
+// faqcs_pair_device, faqcs_render_pair_device, faqcs_inflate_device and faqcs_deflate_device with their faqcs_*_time_ms.  Each is two stages of kernels between the marks of a
 // PackStage; the host statements of the same rules, and the argument checks shared with them, are in faqcs_host.cpp.
 #include "faqcs_ctx.h"
 #include "faqcs_deflate.h"
@@ -94,6 +94,38 @@ extern "C" int faqcs_render_device(faqcs_ctx *c, const faqcs_batch *b, const faq
 }
 
 extern "C" int faqcs_render_time_ms(faqcs_ctx *c, double *scan_ms, double *gather_ms) { return stage_times(c, &faqcs_ctx::render, "faqcs_render_time_ms: no rendering on this context yet", scan_ms, gather_ms); }
+
+static MateDev device_view(const faqcs_mate *m) { const faqcs_batch *b = m->batch; return MateDev{b->seq, b->qual, b->terminal_n, m->text, b->offset, m->def_pos, m->def_len, m->results}; }
+
+extern "C" int faqcs_pair_device(faqcs_ctx *c, const faqcs_mate *m1, const faqcs_mate *m2, uint8_t *d_route, faqcs_pair_info *d_info)
+{
+    if (!c) return fail(FAQCS_E_INVAL, "null ctx");
+    uint32_t n = 0;
+    if (int rc = pair_check_args("faqcs_pair_device", m1, m2, d_route, d_info, &n)) return rc;
+    if (int rc = c->pair.begin(c, faqcs_pair_scratch_bytes(n))) return rc;
+    HIPCHK(faqcs_launch_pair_check(device_view(m1), device_view(m2), n, d_route, c->pair.scratch.p, c->compute));
+    if (int rc = c->pair.mark(1)) return rc;
+    HIPCHK(faqcs_launch_pair_finish(n, m1->results != nullptr, d_route, d_info, c->pair.scratch.p, c->n_cu, c->compute));
+    return c->pair.mark(2);
+}
+
+extern "C" int faqcs_pair_time_ms(faqcs_ctx *c, double *check_ms, double *finish_ms) { return stage_times(c, &faqcs_ctx::pair, "faqcs_pair_time_ms: no pairing on this context yet", check_ms, finish_ms); }
+
+extern "C" int faqcs_render_pair_device(faqcs_ctx *c, int file, const faqcs_mate *m1, const faqcs_mate *m2, const uint8_t *d_route, uint32_t n_pairs,
+                                        const faqcs_render_out *out)
+{
+    if (!c) return fail(FAQCS_E_INVAL, "null ctx");
+    if (int rc = render_pair_check_args("faqcs_render_pair_device", file, m1, m2, d_route, n_pairs, out)) return rc;
+    if (int rc = c->render_pair.begin(c, faqcs_render_scratch_bytes(2u * n_pairs))) return rc;
+    const MateDev a = device_view(m1), b = device_view(m2);
+    HIPCHK(faqcs_launch_render_pair_scan(file, a, b, d_route, n_pairs, out, c->render_pair.scratch.p, c->compute));
+    if (int rc = c->render_pair.mark(1)) return rc;
+    HIPCHK(faqcs_launch_render_pair_gather(file != FAQCS_FILE_DISCARD, a, b, n_pairs, out, c->render_pair.scratch.p, c->prm.input_quality_offset,
+                                           c->prm.output_quality_offset, c->prm.replace_to_N_q, c->n_cu, c->compute));
+    return c->render_pair.mark(2);
+}
+
+extern "C" int faqcs_render_pair_time_ms(faqcs_ctx *c, double *scan_ms, double *gather_ms) { return stage_times(c, &faqcs_ctx::render_pair, "faqcs_render_pair_time_ms: no paired rendering on this context yet", scan_ms, gather_ms); }
 
 extern "C" int faqcs_inflate_device(faqcs_ctx *c, const uint8_t *d_comp, uint64_t n_comp, const uint32_t *d_member_offset, uint32_t n_members, const faqcs_inflate_out *out)
 {

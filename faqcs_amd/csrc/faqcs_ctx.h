@@ -1,6 +1,6 @@
 // faqcs_ctx.h -- internal to the host side of libfaqcs_mi.so (never installed): the context every entry point of include/faqcs_mi.h works
 // on, the launch functions of the kernel files, and the few host functions that cross the host side's translation units:
-//   faqcs_host.cpp       host statements and helpers without HIP (faqcs_host.h)     faqcs_capi_seam.hip  emit / parse / render / inflate / deflate
+//   faqcs_host.cpp       host statements and helpers without HIP (faqcs_host.h)     faqcs_capi_seam.hip  emit / parse / render / pair / inflate / deflate
 //   faqcs_capi.hip       create / destroy, submission, sync, counters, timing       faqcs_capi_comm.hip  RCCL
 //   faqcs_capi_kmer.hip  k-mer groups, the k-mer tails of a submission, faqcs_kmer_*
 // One faqcs_ctx == the (filter_stats, adapter_stats, PlotInfo, Options) quadruple the reference keeps in
@@ -62,6 +62,20 @@ hipError_t faqcs_launch_render_scan(const faqcs_batch *b, const faqcs_read_resul
                                     const uint8_t *select, const uint32_t *order, const faqcs_render_out *out, void *scratch, hipStream_t st);
 hipError_t faqcs_launch_render_gather(const faqcs_batch *b, bool trimmed, const uint8_t *text, const faqcs_render_out *out, const void *scratch,
                                       int in_off, int out_off, uint32_t replace_q, int n_cu, hipStream_t st);
+
+// one mate of faqcs_pair_device / faqcs_render_pair_device, by value (faqcs_pair_kernel.hip)
+struct MateDev {
+    const uint8_t *seq, *qual, *tn, *text;
+    const uint32_t *off, *def_pos, *def_len;
+    const faqcs_read_result *res;
+};
+size_t faqcs_pair_scratch_bytes(uint32_t n_pairs);
+hipError_t faqcs_launch_pair_check(const MateDev &m1, const MateDev &m2, uint32_t n_pairs, uint8_t *route, void *scratch, hipStream_t st);
+hipError_t faqcs_launch_pair_finish(uint32_t n_pairs, bool routed, uint8_t *route, faqcs_pair_info *info, const void *scratch, int n_cu, hipStream_t st);
+hipError_t faqcs_launch_render_pair_scan(int file, const MateDev &m1, const MateDev &m2, const uint8_t *route, uint32_t n_pairs, const faqcs_render_out *out,
+                                         void *scratch, hipStream_t st);
+hipError_t faqcs_launch_render_pair_gather(bool trimmed, const MateDev &m1, const MateDev &m2, uint32_t n_pairs, const faqcs_render_out *out, const void *scratch,
+                                           int in_off, int out_off, uint32_t replace_q, int n_cu, hipStream_t st);
 
 size_t faqcs_inflate_scratch_bytes(uint32_t n_members);
 hipError_t faqcs_launch_inflate_scan(const uint8_t *comp, unsigned long long n_comp, const uint32_t *moff, uint32_t n, const faqcs_inflate_out *out, void *scratch, hipStream_t st);
@@ -154,6 +168,8 @@ struct faqcs_ctx {
     PackStage emit;   // the scan's tile sums and the 16-byte record of every emitted read | scan, gather
     PackStage parse;  // the line index, the record lengths and the two scans' tile sums | index + records, gather
     PackStage render; // the 32-byte descriptor and the text offset of every rendered record, the scan's tile sums | scan, gather
+    PackStage pair;   // the partial of every tile of pairs (first mismatch, sums) | ids + route + partials, finishing block
+    PackStage render_pair; // as render, over the 2 n_pairs candidates of the two mates | scan, gather
     PackStage inflate; // the header fields, the position and the status of every member, the scan's tile sums | scan, decode
     PackStage deflate; // every member's slot, size and position, a block's tokens, the scan's tile sums | encode, gather
     // per-read composition records (trim kernel -> composition_histogram).  Two sets: the histogram kernels of

@@ -1,5 +1,5 @@
 // faqcs_host.cpp -- the part of libfaqcs_mi.so's C ABI (include/faqcs_mi.h) that never touches HIP: the counter layout and the host helpers,
-// the host statements of the parse / render / inflate / deflate rules -- what the GPU tests hold the kernels against -- with their
+// the host statements of the parse / render / pair / inflate / deflate rules -- what the GPU tests hold the kernels against -- with their
 // error texts and argument checks, and the error sink of the whole library.  Plain C++17: it also links into a stand-alone program
 // (tools/host_statements_check.cpp runs it under the sanitizers).
 #include <algorithm>
@@ -342,6 +342,135 @@ extern "C" int faqcs_render_host(const faqcs_params *p, const faqcs_batch *b, co
                 wq[len] = '\n';
                 if (out->rec_offset) out->rec_offset[k + 1] = (uint32_t)(o + size);
                 if (out->rec_index) out->rec_index[k] = i;
+            }
+            o += size; ++k;
+        }
+        if (pass) break;
+        info.n_bytes = o;
+        info.n_reads = k;
+        info.overflow = (o > out->capacity_bytes || o >= (1ull << 32)) ? 1u : 0u;
+        *out->info = info;
+        if (info.overflow) break;
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// the pair stage (include/faqcs_mi.h at faqcs_pair_device)
+// ---------------------------------------------------------------------------------------------------------
+static int mate_check(const std::string &w, const faqcs_mate *m, uint32_t n)
+{
+    if (!m || !m->batch) return fail(FAQCS_E_INVAL, w + ": null mate or batch");
+    if (n && (!m->text || !m->def_pos || !m->def_len)) return fail(FAQCS_E_INVAL, w + ": null text or defline spans");
+    return 0;
+}
+
+int pair_check_args(const char *who, const faqcs_mate *m1, const faqcs_mate *m2, const uint8_t *route, const faqcs_pair_info *info, uint32_t *n)
+{
+    const std::string w(who);
+    if (!m1 || !m2 || !m1->batch || !m2->batch) return fail(FAQCS_E_INVAL, w + ": null mate or batch");
+    if (!info) return fail(FAQCS_E_INVAL, w + ": null info");
+    *n = std::min(m1->batch->n_reads, m2->batch->n_reads);
+    if (*n > 0x7fffffffu) return fail(FAQCS_E_INVAL, w + ": more than 2^31 - 1 pairs must be cut into chunks");
+    if (int rc = mate_check(w, m1, *n)) return rc;
+    if (int rc = mate_check(w, m2, *n)) return rc;
+    if ((m1->results == nullptr) != (m2->results == nullptr)) return fail(FAQCS_E_INVAL, w + ": results of one mate only");
+    if (m1->results && !route) return fail(FAQCS_E_INVAL, w + ": results without a route");
+    return 0;
+}
+
+int render_pair_check_args(const char *who, int file, const faqcs_mate *m1, const faqcs_mate *m2, const uint8_t *route, uint32_t n_pairs, const faqcs_render_out *out)
+{
+    const std::string w(who);
+    if (file < FAQCS_FILE_QC1 || file > FAQCS_FILE_DISCARD) return fail(FAQCS_E_INVAL, w + ": no such file");
+    if (!m1 || !m2 || !m1->batch || !m2->batch || !out) return fail(FAQCS_E_INVAL, w + ": null mate, batch or output");
+    if (!out->text || !out->info) return fail(FAQCS_E_INVAL, w + ": null output text or info");
+    if ((uintptr_t)out->text & 15u) return fail(FAQCS_E_INVAL, w + ": the output text must be 16-byte aligned");
+    if (n_pairs > 0x7fffffffu || n_pairs > m1->batch->n_reads || n_pairs > m2->batch->n_reads) return fail(FAQCS_E_INVAL, w + ": more pairs than a batch has reads, or than 2^31 - 1");
+    for (const faqcs_mate *m : {m1, m2}) {
+        if (!m->def_pos || !m->def_len) return fail(FAQCS_E_INVAL, w + ": null defline spans");
+        if (n_pairs && (!m->text || !m->batch->seq || !m->batch->qual || !m->batch->offset)) return fail(FAQCS_E_INVAL, w + ": null text or batch arrays");
+        if (n_pairs && file != FAQCS_FILE_DISCARD && !m->results) return fail(FAQCS_E_INVAL, w + ": a trimmed file without results");
+    }
+    if (n_pairs && !route) return fail(FAQCS_E_INVAL, w + ": null route");
+    return 0;
+}
+
+// parse_id (trim.cpp:188-222): how many bytes of the defline d[0 .. len) are its id
+static uint32_t id_length(const uint8_t *d, uint32_t len)
+{
+    uint32_t loc = 0;
+    while (loc < len && d[loc] != ' ') ++loc;
+    if (loc > 1 && d[loc - 1] >= '0' && d[loc - 1] <= '9' && (d[loc - 2] == '.' || d[loc - 2] == '/')) loc -= 2;
+    return loc;
+}
+
+// The host statement of the pair rules: the pairs in order up to the first whose ids differ.
+extern "C" int faqcs_pair_host(const faqcs_mate *m1, const faqcs_mate *m2, uint8_t *route, faqcs_pair_info *info)
+{
+    uint32_t n = 0;
+    if (int rc = pair_check_args("faqcs_pair_host", m1, m2, route, info, &n)) return rc;
+    const bool routed = m1->results != nullptr;
+    faqcs_pair_info r{};
+    uint32_t i = 0;
+    for (; i < n; ++i) {
+        const uint8_t *a = m1->text + m1->def_pos[i], *b = m2->text + m2->def_pos[i];
+        const uint32_t la = id_length(a, m1->def_len[i]), lb = id_length(b, m2->def_len[i]);
+        if (la != lb || (la && memcmp(a, b, la) != 0)) { r.mismatch = 1; r.id_len[0] = la; r.id_len[1] = lb; break; }
+        if (!routed) continue;
+        const bool v1 = m1->results[i].flags & FAQCS_F_VALID, v2 = m2->results[i].flags & FAQCS_F_VALID;
+        route[i] = (uint8_t)((v1 ? FAQCS_ROUTE_V1 : 0) | (v2 ? FAQCS_ROUTE_V2 : 0));
+        if (v1 && v2) { r.paired_read_number += 2; r.paired_base_length += (uint64_t)m1->results[i].len + m2->results[i].len; }
+        else if (v1 || v2) ++r.n_one_valid;
+        else ++r.n_none_valid;
+    }
+    r.n_pairs = i;
+    if (routed)
+        for (; i < n; ++i) route[i] = (uint8_t)FAQCS_ROUTE_NOWHERE;
+    *info = r;
+    return 0;
+}
+
+// The host statement of the paired rendering.  Two passes over the candidates, as faqcs_render_host.
+extern "C" int faqcs_render_pair_host(const faqcs_params *p, int file, const faqcs_mate *m1, const faqcs_mate *m2, const uint8_t *route, uint32_t n_pairs,
+                                      const faqcs_render_out *out)
+{
+    if (int rc = render_pair_check_args("faqcs_render_pair_host", file, m1, m2, route, n_pairs, out)) return rc;
+    const bool trimmed = file != FAQCS_FILE_DISCARD;
+    if (trimmed && n_pairs && !p) return fail(FAQCS_E_INVAL, "faqcs_render_pair_host: results without parameters");
+    const faqcs_mate *const mate[2] = {m1, m2};
+    faqcs_render_info info{};
+    for (int pass = 0; pass < 2; ++pass) {
+        uint64_t o = 0;
+        uint32_t k = 0;
+        if (pass && out->rec_offset) out->rec_offset[0] = 0;
+        for (uint64_t j = 0; j < 2ull * n_pairs; ++j) {
+            const uint32_t i = (uint32_t)(j >> 1), s = (uint32_t)(j & 1), r = route[i];
+            const bool take = file == FAQCS_FILE_QC1 ? (s == 0 && r == 3) : file == FAQCS_FILE_QC2 ? (s == 1 && r == 3)
+                            : file == FAQCS_FILE_UNPAIRED ? r == (1u << s) : (r < 4 && !(r >> s & 1u));
+            if (!take) continue;
+            const faqcs_mate &m = *mate[s];
+            const faqcs_batch *b = m.batch;
+            const uint32_t a = b->offset[i], L = b->offset[i + 1] - a;
+            const uint32_t start = trimmed ? m.results[i].start : 0u, len = trimmed ? m.results[i].len : L;
+            if (start + len > L) return fail(FAQCS_E_INVAL, "faqcs_render_pair_host: window outside the read");
+            const uint64_t size = (uint64_t)m.def_len[i] + 2ull * len + 5ull;
+            if (pass) {
+                uint8_t *w = out->text + o;
+                memcpy(w, m.text + m.def_pos[i], m.def_len[i]);
+                w += m.def_len[i];
+                *w++ = '\n';
+                uint8_t *ws = w, *wq = w + len + 3;
+                if (trimmed) {
+                    if (int rc = faqcs_apply_edits(p, b->seq + a, b->qual + a, L, m.results + i, ws, wq)) return rc;
+                } else {
+                    memcpy(ws, b->seq + a, len);
+                    memcpy(wq, b->qual + a, len);
+                }
+                ws[len] = '\n'; ws[len + 1] = '+'; ws[len + 2] = '\n';
+                wq[len] = '\n';
+                if (out->rec_offset) out->rec_offset[k + 1] = (uint32_t)(o + size);
+                if (out->rec_index) out->rec_index[k] = (uint32_t)j;
             }
             o += size; ++k;
         }

@@ -17,11 +17,11 @@
 //           EDIT = false (--replace_to_N_q 0, input offset == output offset: the default, and always for the discard stream) copies;
 //           only flagged reads touch their quality.  EDIT = true with --replace_to_N_q loads the qualities under a piece's bases as well.
 // The kernels use no atomics and only vector stores.
-#include "faqcs_pack_common.h"
+#include "faqcs_render_common.h"
 
 namespace {
 
-using namespace faqcs_pack; // the scans, the terminal-'N' scan, the piece walker, the byte masks and the byte edits
+using namespace faqcs_pack; // the scans, the terminal-'N' scan, the piece walker, the byte masks and the byte edits; RenderPiece (faqcs_render_common.h)
 
 // the inputs of the scan, by value
 struct RenderIn {
@@ -60,8 +60,6 @@ __device__ __forceinline__ uint32_t load_candidates(const RenderIn &I, unsigned 
     }
     return sel;
 }
-
-__device__ __forceinline__ unsigned long long record_bytes(uint32_t dlen, uint32_t len) { return (unsigned long long)dlen + 2ull * len + 5ull; }
 
 __device__ __forceinline__ unsigned long long thread_bytes(uint32_t sel, const uint32_t (&len)[TILE_RPT], const uint32_t (&dlen)[TILE_RPT])
 {
@@ -123,79 +121,6 @@ __global__ __launch_bounds__(TILE_THREADS) void render_scan_apply(const RenderIn
     mark_terminal_extents<2>(I.seq, ra, rb, bits, start, len, kk, desc);
 }
 
-// A piece of the text.  MASKED: the trimmed streams (terminal-'N' quality masking applies); EDIT: G -> N and / or the quality re-base as well
-template <bool MASKED, bool EDIT> struct RenderPiece {
-    const uint8_t *__restrict__ text, *__restrict__ seq, *__restrict__ qual;
-    const uint4 *__restrict__ desc;
-    uint8_t *__restrict__ out_text;
-    int in, out, replace_q;
-    uint32_t in4; // the input offset in every byte
-    uint32_t acc[4];
-
-    __device__ __forceinline__ void clear() { acc[0] = acc[1] = acc[2] = acc[3] = 0; }
-    __device__ __forceinline__ void merge(uint32_t bits, int j, uint32_t v)
-    {
-        const uint32_t m = byte_mask(bits, j);
-        acc[j] = merge_bytes(acc[j], v, m);
-    }
-    __device__ __forceinline__ uint4 record(uint32_t k) const { return desc[2 * (size_t)k]; } // {begin, end, arena position of the window, klo | khi << 16}
-    __device__ __forceinline__ void fill(const uint4 &r, uint32_t k, unsigned long long o, int d, int e, unsigned long long)
-    {
-        const uint4 t = desc[2 * (size_t)k + 1]; // {defline position, defline length, window length, -}
-        const long long rel0 = (long long)o - (long long)r.x; // record position of the piece's byte 0 (>= -15)
-        const long long D = t.y, len = t.z;
-        // record positions: [0, D) defline, D '\n', [D + 1, D + 1 + len) bases, "\n+\n", [D + 4 + len, D + 4 + 2 len) qualities, '\n'
-        const long long ps = D + 1 - rel0, pq = D + 4 + len - rel0; // piece positions of the first base / the first quality
-        const int d_lo = piece_pos(-rel0, d, e), d_hi = piece_pos(D - rel0, d, e);
-        const int s_lo = piece_pos(ps, d, e), s_hi = piece_pos(ps + len, d, e);
-        const int q_lo = piece_pos(pq, d, e), q_hi = piece_pos(pq + len, d, e);
-        const long long plus = ps + len + 1;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const uint32_t m = (d == 0 && e == 16) ? 0xffffffffu : byte_mask(range_bits(d, e), j);
-            acc[j] = merge_bytes(acc[j], 0x0a0a0a0au, m);
-        }
-        if (d_hi > d_lo) {
-            const U128u v = *reinterpret_cast<const U128u *>(text + ((long long)t.x + rel0));
-#pragma unroll
-            for (int j = 0; j < 4; ++j) merge(range_bits(d_lo, d_hi), j, v.w[j]);
-        }
-        if (s_hi > s_lo) {
-            const long long src = (long long)r.z - ps; // piece byte x is window position x - ps
-            const U128u v = *reinterpret_cast<const U128u *>(seq + src);
-            U128u vq = v;
-            if (EDIT && replace_q > 0) vq = *reinterpret_cast<const U128u *>(qual + src);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                uint32_t s = v.w[j], q = vq.w[j];
-                // (a 'G' never lies in a terminal 'N' run: its quality needs no masking here)
-                if (EDIT && replace_q > 0) edit_dword(s, q, in, out, replace_q);
-                merge(range_bits(s_lo, s_hi), j, s);
-            }
-        }
-        if (q_hi > q_lo) {
-            const long long src = (long long)r.z - pq;
-            const U128u v = *reinterpret_cast<const U128u *>(qual + src);
-            const uint32_t klo = r.w & 0xffffu, khi = r.w >> 16;
-            const bool flagged = MASKED && (klo != 0u || (long long)khi != len);
-            // piece bytes that keep their quality: window positions [klo, khi) -> piece bytes [klo + pq, khi + pq)
-            const uint32_t keep = range_bits(piece_pos(pq + klo, q_lo, q_hi), piece_pos(pq + khi, q_lo, q_hi));
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                uint32_t s = 0, q = v.w[j];
-                if (flagged) q = mask_terminal_quality(q, keep, j, in4);
-                if (EDIT) edit_dword(s, q, in, out, 0);
-                merge(range_bits(q_lo, q_hi), j, q);
-            }
-        }
-        if (plus >= d && plus < e) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) merge(1u << (int)plus, j, 0x2b2b2b2bu); // '+'
-        }
-    }
-    __device__ __forceinline__ void store(unsigned long long o) const { *reinterpret_cast<uint4 *>(out_text + o) = make_uint4(acc[0], acc[1], acc[2], acc[3]); }
-};
-
 template <bool MASKED, bool EDIT>
 __global__ __launch_bounds__(GATHER_THREADS) void render_gather(const uint8_t *__restrict__ text, const uint8_t *__restrict__ seq, const uint8_t *__restrict__ qual,
                                                                 const uint4 *__restrict__ desc, const uint32_t *__restrict__ offset,
@@ -203,33 +128,15 @@ __global__ __launch_bounds__(GATHER_THREADS) void render_gather(const uint8_t *_
                                                                 const int in, const int out, const int replace_q)
 {
     if (info->overflow) return;
-    RenderPiece<MASKED, EDIT> p{text, seq, qual, desc, out_text, in, out, replace_q, ((uint32_t)in & 0xffu) * 0x01010101u, {}};
+    RenderPiece<MASKED, EDIT> p{text, seq, qual, nullptr, nullptr, nullptr, desc, out_text, in, out, replace_q, ((uint32_t)in & 0xffu) * 0x01010101u, {}}; // (faqcs_render_common.h)
     for_each_piece_segment(offset, info->n_reads, info->n_bytes, p);
 }
 
 } // namespace
 
-size_t faqcs_render_tile_count(uint32_t n_reads) { return ((size_t)n_reads + TILE_ITEMS - 1) / TILE_ITEMS; }
+size_t faqcs_render_tile_count(uint32_t n_reads) { return render_tile_count(n_reads); }
 // descriptors (32 bytes per read), record offsets (n_reads + 1), tile prefixes, tile sums
-size_t faqcs_render_scratch_bytes(uint32_t n_reads)
-{
-    const size_t nt = faqcs_render_tile_count(n_reads);
-    return (size_t)n_reads * 2 * sizeof(uint4) + nt * sizeof(TilePrefix) + nt * sizeof(TileSum) + ((size_t)n_reads + 1) * sizeof(uint32_t) + 64;
-}
-
-namespace {
-struct Scratch { uint4 *desc; TilePrefix *prefix; TileSum *tiles; uint32_t *offs; };
-Scratch carve(void *scratch, uint32_t n_reads)
-{
-    const size_t nt = faqcs_render_tile_count(n_reads);
-    Scratch s;
-    s.desc = reinterpret_cast<uint4 *>(scratch);
-    s.prefix = reinterpret_cast<TilePrefix *>(s.desc + 2 * (size_t)n_reads);
-    s.tiles = reinterpret_cast<TileSum *>(s.prefix + nt);
-    s.offs = reinterpret_cast<uint32_t *>(s.tiles + nt);
-    return s;
-}
-} // namespace
+size_t faqcs_render_scratch_bytes(uint32_t n_reads) { return render_scratch_bytes(n_reads); }
 
 // scratch: faqcs_render_scratch_bytes(n_reads) bytes, 16-byte aligned.  The scan: totals, overflow decision, rec_offset / rec_index, the descriptors.
 hipError_t faqcs_launch_render_scan(const faqcs_batch *b, const faqcs_read_result *res, const uint32_t *def_pos, const uint32_t *def_len,
@@ -237,7 +144,7 @@ hipError_t faqcs_launch_render_scan(const faqcs_batch *b, const faqcs_read_resul
 {
     const uint32_t n = b->n_reads;
     const size_t nt = faqcs_render_tile_count(n);
-    const Scratch s = carve(scratch, n);
+    const RenderScratch s = render_carve(scratch, n);
     const RenderIn I{b->seq, b->offset, b->terminal_n, res, def_pos, def_len, select, order, n};
     if (nt) hipLaunchKernelGGL(render_tile_totals, dim3((unsigned)nt), dim3(TILE_THREADS), 0, st, I, s.tiles);
     hipLaunchKernelGGL(scan_tile_sums<faqcs_render_info>, dim3(1), dim3(SCAN_THREADS), 0, st, s.tiles, (uint32_t)nt, s.prefix, (unsigned long long)out->capacity_bytes, out->info, s.offs, out->rec_offset);
@@ -250,7 +157,7 @@ hipError_t faqcs_launch_render_gather(const faqcs_batch *b, bool trimmed, const 
                                       int in_off, int out_off, uint32_t replace_q, int n_cu, hipStream_t st)
 {
     const uint32_t n = b->n_reads;
-    const Scratch s = carve(const_cast<void *>(scratch), n);
+    const RenderScratch s = render_carve(const_cast<void *>(scratch), n);
     // the text cannot exceed min(capacity, 2^32 - 1) bytes
     const unsigned grid = gather_grid(out->capacity_bytes < 0xffffffffull ? out->capacity_bytes : 0xffffffffull, n_cu);
     if (!grid || !n) return hipSuccess;

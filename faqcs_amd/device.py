@@ -1,5 +1,6 @@
 """Torch-facing helpers of the device seam: inputs and outputs are torch tensors that live on the GPU; the work is the
-library's HIP kernels (faqcs_emit_device, faqcs_render_device, faqcs_inflate_device, faqcs_deflate_device), never torch ops."""
+library's HIP kernels (faqcs_emit_device, faqcs_render_device, faqcs_pair_device, faqcs_render_pair_device, faqcs_inflate_device,
+faqcs_deflate_device), never torch ops."""
 import ctypes as C
 
 from . import _capi as capi
@@ -79,6 +80,86 @@ def rendered_fastq(engine, text, def_pos, def_len, seq, qual, offset, results=No
     if overflow:
         raise FaqcsError(capi.E_INVAL, "faqcs_render_device: the text needs %d bytes, the output holds %d" % (n_bytes, cap))
     return o_text[shift:shift + n_bytes], o_off[:n_rec + 1]
+
+
+class DeviceMate:
+    """One mate of a paired run in device memory, as faqcs_parse_device + faqcs_submit_device left it: text (uint8 CUDA tensor whose element
+    0 is byte 0 of the text the parse indexed, with that text's padding), def_pos / def_len (int32 / uint32 [n]), seq / qual / offset /
+    terminal_n (the batch, as for rendered_fastq()), results (the (n, 4) int16 tensor of the submission, or None before it)."""
+
+    def __init__(self, text, def_pos, def_len, seq, qual, offset, results=None, terminal_n=None):
+        self.text, self.def_pos, self.def_len, self.seq, self.qual, self.offset = text, def_pos, def_len, seq, qual, offset
+        self.results, self.terminal_n = results, terminal_n
+        self.n = int(offset.numel()) - 1
+
+    def capi(self):
+        """-> capi.Mate (it keeps its capi.Batch alive)"""
+        n = self.n
+        b = capi.Batch(self.seq.data_ptr(), self.qual.data_ptr(), self.offset.data_ptr(), n, 0, None, 0,
+                       self.terminal_n.data_ptr() if self.terminal_n is not None and n else None)
+        m = capi.Mate(C.pointer(b), self.results.data_ptr() if self.results is not None else None, self.text.data_ptr(),
+                      self.def_pos.data_ptr(), self.def_len.data_ptr())
+        m._batch = b
+        return m
+
+
+def pair_route(engine, mate1, mate2):
+    """The pair stage of two device-resident mates (DeviceMate each; faqcs_pair_device): the id check of FaQCs.cpp:382-389, the route of
+    every pair and the two FilterStat slots that depend on both mates.  With results on neither mate only the ids are checked and route is
+    None.  Returns (route, info): uint8 CUDA tensor [min(n1, n2)] of capi.ROUTE_* bits (pairs behind a mismatch: ROUTE_NOWHERE) and a dict
+    of the faqcs_pair_info fields; with info["mismatch"] the ids of pair info["n_pairs"] are the first info["id_len"][s] bytes of mate s's
+    defline, and info["ids"] holds them (downloaded for the reference's message)."""
+    import torch
+
+    dev = mate1.text.device
+    n = min(mate1.n, mate2.n)
+    routed = mate1.results is not None
+    route = torch.empty(max(n, 1), dtype=torch.uint8, device=dev) if routed else None
+    d_info = torch.zeros(5, dtype=torch.int64, device=dev)
+    torch.cuda.current_stream(dev).synchronize()  # the library's compute stream is its own: the inputs must be complete
+    engine.pair_device(mate1.capi(), mate2.capi(), route.data_ptr() if routed else None, d_info.data_ptr())
+    engine.sync()
+    p = capi.PairInfo.from_buffer_copy(d_info.cpu().numpy().tobytes())
+    info = {f: int(getattr(p, f)) for f, _ in capi.PairInfo._fields_ if f != "id_len"}
+    info["id_len"] = (int(p.id_len[0]), int(p.id_len[1]))
+    if info["mismatch"]:
+        i = info["n_pairs"]
+        info["ids"] = tuple(bytes(m.text[int(m.def_pos[i]) & 0xFFFFFFFF:(int(m.def_pos[i]) & 0xFFFFFFFF) + ln].cpu().numpy())
+                            for m, ln in zip((mate1, mate2), info["id_len"]))
+    return (route[:n] if routed else None), info
+
+
+def paired_files(engine, mate1, mate2, route, n_pairs, files=(capi.FILE_QC1, capi.FILE_QC2, capi.FILE_UNPAIRED, capi.FILE_DISCARD), capacity=None):
+    """The FASTQ text of the files of a paired run from two device-resident mates (DeviceMate each) and the route pair_route() delivered,
+    assembled on the device (faqcs_render_pair_device, one call per file).  files: capi.FILE_* codes; capacity: bytes of text to make room
+    for per file (default: both input texts plus 5 bytes per read, which no file exceeds).
+    Returns {file: (text, rec_offset)}: uint8 [n_bytes] -- a view that starts 16-byte aligned --, int32 [n_rendered + 1] (bit pattern of uint32)."""
+    import torch
+
+    dev = mate1.text.device
+    n_pairs = int(n_pairs)
+    cap = int(mate1.text.numel()) + int(mate2.text.numel()) + 10 * n_pairs if capacity is None else int(capacity)
+    m1, m2 = mate1.capi(), mate2.capi()
+    torch.cuda.current_stream(dev).synchronize()  # the library's compute stream is its own: the inputs must be complete
+    outs = {}
+    for f in files:
+        o_text = torch.empty(cap + capi.ARENA_PAD_AFTER + 16, dtype=torch.uint8, device=dev)
+        o_off = torch.empty(2 * n_pairs + 1, dtype=torch.int32, device=dev)
+        info = torch.zeros(2, dtype=torch.int64, device=dev)
+        shift = (-o_text.data_ptr()) % 16
+        out = capi.RenderOut(o_text.data_ptr() + shift, cap, o_off.data_ptr(), None, info.data_ptr())
+        torch.cuda.current_stream(dev).synchronize()
+        engine.render_pair_device(f, m1, m2, route.data_ptr() if n_pairs else None, n_pairs, out)
+        outs[f] = (o_text, o_off, info, shift)
+    engine.sync()
+    res = {}
+    for f, (o_text, o_off, info, shift) in outs.items():
+        h = info.cpu().numpy()
+        n_bytes, n_rec, overflow = int(h[0]), int(h[1]) & 0xFFFFFFFF, int(h[1]) >> 32
+        if overflow:
+            raise FaqcsError(capi.E_INVAL, "faqcs_render_pair_device: the text needs %d bytes, the output holds %d" % (n_bytes, cap))
+        res[f] = (o_text[shift:shift + n_bytes], o_off[:n_rec + 1])
+    return res
 
 
 def inflated_text(engine, comp, member_offset=None, capacity=None):

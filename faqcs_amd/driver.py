@@ -252,6 +252,72 @@ def render_model(opt, in_off, text, def_pos, def_len, seq, qual, offset, res=Non
     return out, rec_offset.astype(np.uint32), index.astype(np.uint32)
 
 
+def pair_model(mate1, mate2):
+    """What faqcs_pair_device() / faqcs_pair_host() deliver, written from parse_id (trim.cpp:188-222) and FaQCs.cpp:296-361,382-389: a mate
+    is a dict with text (uint8), def_pos, def_len and res (the per-read results, or None for both mates: check only).  The pairs
+    i < min(n1, n2) in order; the first whose ids differ stops the count and routes the rest nowhere.
+    -> (route uint8[n] or None, info dict of the faqcs_pair_info fields)"""
+    n = min(len(mate1["def_pos"]), len(mate2["def_pos"]))
+    routed = mate1["res"] is not None
+    route = np.full(n, capi.ROUTE_NOWHERE, dtype=np.uint8) if routed else None
+    info = dict(paired_read_number=0, paired_base_length=0, n_pairs=n, mismatch=0, id_len=(0, 0), n_one_valid=0, n_none_valid=0)
+    for i in range(n):
+        ids = []
+        for m in (mate1, mate2):
+            a = int(m["def_pos"][i])
+            ids.append(parse_id(bytes(m["text"][a:a + int(m["def_len"][i])])))
+        if ids[0] != ids[1]:
+            info.update(n_pairs=i, mismatch=1, id_len=(len(ids[0]), len(ids[1])))
+            break
+        if not routed:
+            continue
+        v1, v2 = (bool(m["res"]["flags"][i] & capi.F_VALID) for m in (mate1, mate2))
+        route[i] = (capi.ROUTE_V1 if v1 else 0) | (capi.ROUTE_V2 if v2 else 0)
+        if v1 and v2:  # FaQCs.cpp:304-308
+            info["paired_read_number"] += 2
+            info["paired_base_length"] += int(mate1["res"]["len"][i]) + int(mate2["res"]["len"][i])
+        elif v1 or v2:
+            info["n_one_valid"] += 1
+        else:
+            info["n_none_valid"] += 1
+    return route, info
+
+
+def render_pair_model(opt, in_off, file, mate1, mate2, route, n_pairs):
+    """What faqcs_render_pair_device() / faqcs_render_pair_host() write for one of the four files (capi.FILE_*), from FaQCs.cpp:296-361: both
+    mates to QC.1 / QC.2 when both are valid, the one valid mate to QC.unpaired, every mate that is not valid to QC.discard as it came --
+    pair by pair, mate 1 first.  A mate is a dict with text, def_pos, def_len, seq, qual, offset, res.
+    -> (text uint8, rec_offset uint32[n_rendered + 1], rec_index uint32[n_rendered], rec_index[k] = 2 i + s)"""
+    mates = (mate1, mate2)
+    trimmed = file != capi.FILE_DISCARD
+    edited = [edited_arenas(opt, in_off, m["seq"], m["qual"], m["offset"]) if trimmed else (np.asarray(m["seq"]), np.asarray(m["qual"])) for m in mates]
+    pieces, ends, index = [], [0], []
+    for i in range(n_pairs):
+        r = int(route[i])
+        for s, m in enumerate(mates):
+            if file == capi.FILE_QC1:
+                take = s == 0 and r == 3
+            elif file == capi.FILE_QC2:
+                take = s == 1 and r == 3
+            elif file == capi.FILE_UNPAIRED:
+                take = r == (1 << s)
+            else:
+                take = r < 4 and not (r >> s) & 1
+            if not take:
+                continue
+            a, b = int(m["offset"][i]), int(m["offset"][i + 1])
+            if trimmed:
+                a += int(m["res"]["start"][i])
+                b = a + int(m["res"]["len"][i])
+            d = int(m["def_pos"][i])
+            rec = (np.asarray(m["text"][d:d + int(m["def_len"][i])]).tobytes() + b"\n" + edited[s][0][a:b].tobytes() + b"\n+\n"
+                   + edited[s][1][a:b].tobytes() + b"\n")
+            pieces.append(rec)
+            ends.append(ends[-1] + len(rec))
+            index.append(2 * i + s)
+    return np.frombuffer(b"".join(pieces), dtype=np.uint8), np.asarray(ends, dtype=np.uint32), np.asarray(index, dtype=np.uint32)
+
+
 class Run:
     """State the reference keeps in main(): filter_stats, adapter_stats, PlotInfo, Options (FaQCs.cpp:67-69)."""
 

@@ -124,6 +124,30 @@ class HipEngine:
         _check(self.lib, self.lib.faqcs_render_time_ms(self.ctx, C.byref(a), C.byref(g)))
         return a.value, g.value
 
+    def pair_device(self, mate1, mate2, d_route, d_info):
+        """faqcs_pair_device: the id check, the route and the pair counters of two device-resident mates (capi.Mate each: a host capi.Batch of
+        device pointers, the device results or None, the text and the defline spans faqcs_parse_device delivered) into d_route (uint8
+        [min of the two n_reads]; None with both results None: check only) and d_info (a faqcs_pair_info in device memory).  Enqueued; sync() waits."""
+        _check(self.lib, self.lib.faqcs_pair_device(self.ctx, C.byref(mate1), C.byref(mate2), d_route, d_info))
+
+    def pair_time_ms(self):
+        """(check ms, finish ms) of the last pair_device() on this engine (HIP events on the compute stream); waits for it."""
+        a, g = C.c_double(), C.c_double()
+        _check(self.lib, self.lib.faqcs_pair_time_ms(self.ctx, C.byref(a), C.byref(g)))
+        return a.value, g.value
+
+    def render_pair_device(self, file, mate1, mate2, d_route, n_pairs, out):
+        """faqcs_render_pair_device: the FASTQ text of one of the four files of a paired run (capi.FILE_*) from the two mates and the route
+        pair_device() wrote, into the arrays of `out` (a capi.RenderOut of device pointers; rec_offset / rec_index hold up to 2 n_pairs
+        (+ 1) entries).  Enqueued; sync() waits."""
+        _check(self.lib, self.lib.faqcs_render_pair_device(self.ctx, int(file), C.byref(mate1), C.byref(mate2), d_route, int(n_pairs), C.byref(out)))
+
+    def render_pair_time_ms(self):
+        """(scan ms, gather ms) of the last render_pair_device() on this engine (HIP events on the compute stream); waits for it."""
+        a, g = C.c_double(), C.c_double()
+        _check(self.lib, self.lib.faqcs_render_pair_time_ms(self.ctx, C.byref(a), C.byref(g)))
+        return a.value, g.value
+
     def inflate_device(self, d_comp, n_comp, d_member_offset, n_members, out):
         """faqcs_inflate_device: BGZF members in device memory (d_comp: device address, any alignment; d_member_offset: device uint32
         [n_members + 1], as bgzf_index_host() found them) -> their text in the arrays of `out` (a capi.InflateOut of device pointers).

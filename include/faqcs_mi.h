@@ -35,7 +35,8 @@ extern "C" {
  * faqcs_emit_device (the trimmed, edited reads packed on the device) is a new entry point with structures of its own, and so are
  * faqcs_parse_device / faqcs_parse_host (FASTQ text to a packed batch) and faqcs_render_device / faqcs_render_host (the FASTQ text of the
  * output files), and faqcs_inflate_device / faqcs_inflate_host / faqcs_bgzf_index_host (BGZF members to that text),
- * and faqcs_deflate_device / faqcs_deflate_host (text to BGZF members). */
+ * and faqcs_deflate_device / faqcs_deflate_host (text to BGZF members), and faqcs_pair_device / faqcs_pair_host /
+ * faqcs_render_pair_device / faqcs_render_pair_host (the two mates of a paired run from two batches). */
 #define FAQCS_ABI_VERSION 2
 
 /* FilterStat enum order, FaQCs.h:46-75 */
@@ -332,7 +333,8 @@ int  faqcs_parse_host(const uint8_t *text, uint64_t n_text, int final, const faq
  * behind the last defline), the arenas that of faqcs_batch.  The call is enqueued on the context's compute stream behind the submission and
  * returns at once: the host never waits for a count; faqcs_sync() waits.  With both mates of a paired run in one batch -- read i of mate 2
  * at m + i -- the four files are four calls: QC.1 select [v1 & v2, 0], QC.2 select [0, v1 & v2], unpaired select
- * [v1 ^ v2, v1 ^ v2] in the order [0, m, 1, m + 1, ...], discard without results, select [!v1, !v2] in the same order.
+ * [v1 ^ v2, v1 ^ v2] in the order [0, m, 1, m + 1, ...], discard without results, select [!v1, !v2] in the same order.  (The two mates in
+ * TWO batches, as two parses leave them: faqcs_pair_device / faqcs_render_pair_device below.)
  * Scratch (36 bytes per read) is the library's: grown on demand, freed by faqcs_destroy().
  * FAQCS_E_INVAL: a null ctx / batch / d_text (with reads) / batch arrays (with reads) / d_def_pos / d_def_len / out / out->text / out->info,
  * or out->text not 16-byte aligned.
@@ -353,6 +355,72 @@ int  faqcs_render_device(faqcs_ctx *ctx, const faqcs_batch *batch, const faqcs_r
 int  faqcs_render_host(const faqcs_params *p, const faqcs_batch *batch, const faqcs_read_result *results,
                        const uint8_t *text, const uint32_t *def_pos, const uint32_t *def_len,
                        const uint8_t *select, const uint32_t *order, const faqcs_render_out *out);
+
+/* The pair stage of the device seam: the two mates of a paired run (-1 r1 -2 r2) in TWO batches -- two texts, two sets of defline spans,
+ * two result arrays, as two faqcs_parse_device + faqcs_submit_device calls leave them -- checked, routed and rendered without joining them.
+ * A faqcs_mate is one mate's buffer: batch (seq / qual / offset / terminal_n as for faqcs_render_device; segment_start is not needed), the
+ * results of its submission, the text its parse indexed (with that text's padding) and the defline spans.  The faqcs_mate structs and the
+ * faqcs_batch they point to are HOST memory; for the device forms every other pointer in them is a DEVICE pointer.
+ *
+ * faqcs_pair_device / faqcs_pair_host: the id check of FaQCs.cpp:382-389, the routing of FaQCs.cpp:296-361 and the two FilterStat slots
+ * that depend on both mates (FaQCs.cpp:304-308).
+ *   - size.  n = min(m1->batch->n_reads, m2->batch->n_reads).  Unequal counts are no error: chunks of two files differ, and the caller
+ *     carries the surplus.  n > 2^31 - 1 is FAQCS_E_INVAL.
+ *   - the id (parse_id, trim.cpp:188-222) of a defline of len bytes is its first loc bytes: loc is the position of the first ' ', or len
+ *     if there is none; loc is reduced by 2 when loc > 1, byte loc - 1 is '0'..'9' and byte loc - 2 is '.' or '/'.  A tab is no delimiter;
+ *     an empty defline has the empty id.  Pair i MATCHES when both ids have the same length and the same bytes.
+ *   - errors are sequential, as everywhere in the seam: the lowest i that does not match decides.  mismatch = 1, n_pairs = i and id_len[]
+ *     holds the two id lengths -- the ids are text[def_pos[i] .. + id_len), for the caller to download for the reference's message.
+ *     Without a mismatch n_pairs = n and id_len[] = 0.
+ *   - the route.  route[i] for i < n_pairs is FAQCS_ROUTE_V1 * valid1 | FAQCS_ROUTE_V2 * valid2, valid = results[i].flags & FAQCS_F_VALID;
+ *     route[i] for n_pairs <= i < n is FAQCS_ROUTE_NOWHERE.  The counters (paired_read_number, paired_base_length, n_one_valid,
+ *     n_none_valid) cover i < n_pairs only.  Nothing outside route[0 .. n) and info is written.
+ *   - check only.  With both results == NULL only the id check runs -- the reference's order: the check comes before trim(), so a caller can
+ *     check before submitting.  route may then be NULL and is not touched; the counters and n_one_valid / n_none_valid are 0.  Exactly one
+ *     results == NULL, or results without a route, is FAQCS_E_INVAL.
+ *   - the bytes of info and route are a function of the inputs alone: the kernels use no atomics (per-tile partials, one finishing block).
+ * faqcs_pair_device is enqueued on the context's compute stream and returns at once; d_route and d_info are DEVICE pointers.  The texts
+ * need the padding faqcs_parse_device() asks for (whole 16-byte vectors are loaded at a defline's start and over its end).
+ * FAQCS_E_INVAL: a null ctx / mate / batch / info, null text / def_pos / def_len with n > 0, and what is listed above.
+ *
+ * faqcs_render_pair_device / faqcs_render_pair_host: one of the four files of FaQCs.cpp:296-361 from the two mates and the route.  The
+ * candidates are j = 0 .. 2 n_pairs - 1, pair i = j >> 1, mate s = j & 1, in that order; with r = route[i] candidate j is rendered when
+ *     FAQCS_FILE_QC1       s == 0 && r == 3              the trimmed record (Run::write_read: as faqcs_render_device with results)
+ *     FAQCS_FILE_QC2       s == 1 && r == 3              trimmed
+ *     FAQCS_FILE_UNPAIRED  r == (1 << s)                 trimmed
+ *     FAQCS_FILE_DISCARD   r < 4 && !(r >> s & 1)        the ORIGINAL record (as faqcs_render_device without results; results are not read)
+ * so a pair routed FAQCS_ROUTE_NOWHERE appears in no file.  Bases, qualities, defline, result and terminal_n of a record come from mate s's
+ * own arrays; rec_index[k] = 2 i + s; rec_offset / rec_index hold up to 2 n_pairs (+ 1) entries.  info, the overflow rule (nothing but
+ * info is written), the touched ranges, the alignment demands and the FAQCS_E_INVAL list are those of faqcs_render_device, per mate; in
+ * addition a file code outside 0 .. 3, n_pairs larger than either batch's n_reads or than 2^31 - 1, a null route with n_pairs > 0 and null
+ * results for a trimmed file with n_pairs > 0 are FAQCS_E_INVAL.  n_pairs = 0 yields zeros and rec_offset[0] = 0.  The device form takes
+ * its parameters from the context, is enqueued on the compute stream and returns at once; scratch (72 bytes per pair) is the library's.
+ * The host forms are the host statements of these rules: plain single-threaded C++, no HIP call, no padding needed, exact write ranges. */
+typedef struct faqcs_mate {
+    const faqcs_batch *batch;            /* seq / qual / offset / terminal_n: as for faqcs_render_device; segment_start not needed */
+    const faqcs_read_result *results;    /* n_reads entries; NULL only where stated */
+    const uint8_t  *text;                /* the text the parse indexed, with its padding */
+    const uint32_t *def_pos, *def_len;
+} faqcs_mate;
+
+typedef struct faqcs_pair_info {
+    uint64_t paired_read_number;         /* FaQCs.cpp:306: += 2 per pair with both mates valid */
+    uint64_t paired_base_length;         /* FaQCs.cpp:307: += len1 + len2 of those pairs (faqcs_read_result.len) */
+    uint32_t n_pairs;                    /* pairs routed (== index of the bad pair when mismatch != 0) */
+    uint32_t mismatch;                   /* 1: the ids of pair n_pairs differ */
+    uint32_t id_len[2];                  /* mismatch: parse_id length of that pair's two deflines (the ids the reference prints), else 0 */
+    uint32_t n_one_valid, n_none_valid;  /* pairs with exactly one / no valid mate, among the routed */
+} faqcs_pair_info;
+
+enum { FAQCS_ROUTE_V1 = 1, FAQCS_ROUTE_V2 = 2, FAQCS_ROUTE_NOWHERE = 0x80 };
+enum { FAQCS_FILE_QC1 = 0, FAQCS_FILE_QC2, FAQCS_FILE_UNPAIRED, FAQCS_FILE_DISCARD };
+
+int  faqcs_pair_device(faqcs_ctx *ctx, const faqcs_mate *m1, const faqcs_mate *m2, uint8_t *d_route, faqcs_pair_info *d_info);
+int  faqcs_pair_host(const faqcs_mate *m1, const faqcs_mate *m2, uint8_t *route, faqcs_pair_info *info);
+int  faqcs_render_pair_device(faqcs_ctx *ctx, int file, const faqcs_mate *m1, const faqcs_mate *m2,
+                              const uint8_t *d_route, uint32_t n_pairs, const faqcs_render_out *out);
+int  faqcs_render_pair_host(const faqcs_params *p, int file, const faqcs_mate *m1, const faqcs_mate *m2,
+                            const uint8_t *route, uint32_t n_pairs, const faqcs_render_out *out);
 
 /* The step in front of the device seam: compressed input.  BGZF (bgzip) members in device memory -> the FASTQ text faqcs_parse_device()
  * takes.  Ordinary single-stream gzip is not taken: it has no member boundaries (the command line's faqcs_pargz.h handles it on the host).
@@ -606,6 +674,10 @@ int  faqcs_emit_time_ms(faqcs_ctx *ctx, double *scan_ms, double *gather_ms);
 int  faqcs_parse_time_ms(faqcs_ctx *ctx, double *index_ms, double *gather_ms);
 /* the same for the LAST faqcs_render_device() on the context: the scan (scan_ms), the gather (gather_ms) */
 int  faqcs_render_time_ms(faqcs_ctx *ctx, double *scan_ms, double *gather_ms);
+/* the same for the LAST faqcs_pair_device() on the context: the ids, the route and the tile partials (check_ms), the finishing block (finish_ms) */
+int  faqcs_pair_time_ms(faqcs_ctx *ctx, double *check_ms, double *finish_ms);
+/* the same for the LAST faqcs_render_pair_device() on the context: the scan (scan_ms), the gather (gather_ms) */
+int  faqcs_render_pair_time_ms(faqcs_ctx *ctx, double *scan_ms, double *gather_ms);
 /* the same for the LAST faqcs_inflate_device() on the context: the scan of the headers (scan_ms), the decode with its CRC and the status (decode_ms) */
 int  faqcs_inflate_time_ms(faqcs_ctx *ctx, double *scan_ms, double *decode_ms);
 /* the same for the LAST faqcs_deflate_device() on the context: the members' encoding into their slots (encode_ms), sizes, positions and the gather (gather_ms) */
