@@ -186,6 +186,24 @@ class _Spans:
         self.offset = np.zeros(self.n + 1, np.uint32)
 
 
+HOSTILE_PAD = b"/1 a9.2x"
+
+
+def spans_on_device(dev, m):
+    """A mate of deflines alone (text, def_pos, def_len, n) for the id check: the text with 64 bytes of HOSTILE_PAD in front of it and behind
+    it (the pattern begins anew right behind the text).  -> (capi.Mate, what has to stay alive)"""
+    import torch
+
+    h = np.resize(np.frombuffer(HOSTILE_PAD, np.uint8), 64 + len(m.text) + 64).copy()
+    h[64 + len(m.text):64 + len(m.text) + 8] = np.frombuffer(HOSTILE_PAD, np.uint8)
+    h[64:64 + len(m.text)] = m.text
+    t = torch.from_numpy(h).to(dev)
+    dpos = torch.from_numpy(np.concatenate([m.def_pos, np.zeros(1, np.uint32)]).view(np.int32)).to(dev)
+    dlen = torch.from_numpy(np.concatenate([m.def_len, np.zeros(1, np.uint32)]).view(np.int32)).to(dev)
+    bt = capi.Batch(None, None, None, m.n, 0, None, 0, None)
+    return capi.Mate(C.pointer(bt), None, t.data_ptr() + 64, dpos.data_ptr(), dlen.data_ptr()), [t, dpos, dlen, bt]
+
+
 def test_deflines_at_the_ends_of_the_text_and_of_every_length():
     """Check only, on texts that are nothing but deflines: position 0, the text's last byte, a 0-byte defline next to one of 300, and every
     catalogue entry both ways round; the bytes in front of the text and the 64 behind it ("/1 a9.2x" ...) would change verdicts if they were read as part of a defline."""
@@ -204,15 +222,9 @@ def test_deflines_at_the_ends_of_the_text_and_of_every_length():
         _, want = pcs.pair_host(eng.lib, pc, with_res=False)
         keep, mates = [], []
         for m in (a, b):
-            h = np.resize(np.frombuffer(b"/1 a9.2x", np.uint8), 64 + len(m.text) + 64).copy()
-            h[64 + len(m.text):64 + len(m.text) + 8] = np.frombuffer(b"/1 a9.2x", np.uint8)
-            h[64:64 + len(m.text)] = m.text
-            t = torch.from_numpy(h).to(dev)
-            dpos = torch.from_numpy(np.concatenate([m.def_pos, np.zeros(1, np.uint32)]).view(np.int32)).to(dev)
-            dlen = torch.from_numpy(np.concatenate([m.def_len, np.zeros(1, np.uint32)]).view(np.int32)).to(dev)
-            bt = capi.Batch(None, None, None, m.n, 0, None, 0, None)
-            keep += [t, dpos, dlen, bt]
-            mates.append(capi.Mate(C.pointer(bt), None, t.data_ptr() + 64, dpos.data_ptr(), dlen.data_ptr()))
+            mate, alive = spans_on_device(dev, m)
+            keep += alive
+            mates.append(mate)
         _, got, _ = pair_dev(eng, mates[0], mates[1], len(pairs), with_res=False, with_route=False)
         assert got == want, pairs[want["n_pairs"]] if want["mismatch"] else None
         return got
