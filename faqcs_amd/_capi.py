@@ -123,6 +123,9 @@ class DeflateOut(C.Structure):
     _fields_ = [("comp", C.c_void_p), ("capacity_bytes", C.c_uint64), ("member_offset", C.c_void_p), ("info", C.c_void_p)]
 
 
+DEFLATE_FAST, DEFLATE_DENSE = 0, 1  # FAQCS_DEFLATE_*: the match finder of faqcs_deflate_device_mode / faqcs_deflate_host_mode
+
+
 # FAQCS_PARSE_*: faqcs_parse_info.error, the error of record n_reads
 PARSE_OK, PARSE_E_SEQUENCE, PARSE_E_PLUS, PARSE_E_PLUS_DELIM, PARSE_E_QUALITY, PARSE_E_LENGTH = range(6)
 
@@ -250,6 +253,8 @@ def load_library():
         "faqcs_inflate_time_ms": (i32, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "faqcs_deflate_device": (i32, [vp, vp, u64, u32, i32, C.POINTER(DeflateOut)]),
         "faqcs_deflate_host": (i32, [vp, u64, u32, i32, C.POINTER(DeflateOut)]),
+        "faqcs_deflate_device_mode": (i32, [vp, vp, u64, u32, i32, i32, C.POINTER(DeflateOut)]),
+        "faqcs_deflate_host_mode": (i32, [vp, u64, u32, i32, i32, C.POINTER(DeflateOut)]),
         "faqcs_deflate_time_ms": (i32, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "faqcs_submit_async": (i32, [vp, C.POINTER(Batch), vp, C.POINTER(u64)]),
         "faqcs_wait": (i32, [vp, u64]),

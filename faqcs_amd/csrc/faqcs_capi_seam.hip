@@ -142,12 +142,17 @@ extern "C" int faqcs_inflate_time_ms(faqcs_ctx *c, double *scan_ms, double *deco
 
 extern "C" int faqcs_deflate_device(faqcs_ctx *c, const uint8_t *d_text, uint64_t n_text, uint32_t member_bytes, int final, const faqcs_deflate_out *out)
 {
+    return faqcs_deflate_device_mode(c, d_text, n_text, member_bytes, final, FAQCS_DEFLATE_FAST, out);
+}
+
+extern "C" int faqcs_deflate_device_mode(faqcs_ctx *c, const uint8_t *d_text, uint64_t n_text, uint32_t member_bytes, int final, int mode, const faqcs_deflate_out *out)
+{
     if (!c) return fail(FAQCS_E_INVAL, "null ctx");
-    if (int rc = deflate_check_args("faqcs_deflate_device", d_text, n_text, member_bytes, final, out)) return rc;
+    if (int rc = deflate_check_args("faqcs_deflate_device", d_text, n_text, member_bytes, final, mode, out)) return rc;
     const uint32_t mb = member_bytes ? member_bytes : (uint32_t)faqcs_deflate::MAX_TEXT;
     const uint32_t n_data = (uint32_t)((n_text + mb - 1) / mb), n = n_data + (final ? 1u : 0u);
     if (int rc = c->deflate.begin(c, faqcs_deflate_scratch_bytes(n, n_data, mb, c->n_cu))) return rc;
-    HIPCHK(faqcs_launch_deflate_encode(d_text, n_text, mb, n, n_data, c->deflate.scratch.p, c->n_cu, c->compute));
+    HIPCHK(faqcs_launch_deflate_encode(d_text, n_text, mb, n, n_data, mode, c->deflate.scratch.p, c->n_cu, c->compute));
     if (int rc = c->deflate.mark(1)) return rc;
     HIPCHK(faqcs_launch_deflate_gather(mb, n, n_data, out, c->deflate.scratch.p, c->n_cu, c->compute));
     return c->deflate.mark(2);

@@ -16,6 +16,16 @@
 //              (where the last token of the tile in front ended).  Reachability is marked by pointer jumping -- 10 doublings -- which
 //              gives exactly the set a serial walk gives.
 //     tokens   every token start writes its token to tok[p] (global scratch: 4 bytes per position) and counts its symbols
+//   MODE_DENSE replaces `find` (deflate_member<MODE_DENSE>; MODE_FAST is everything above, untouched).  The tile is looked up and entered in
+//   SUB-TILES of 256 positions, in order, so that the tables a position sees hold exactly the positions in front of its own sub-tile:
+//     find     four lanes per position, one candidate each: (a) head16[0], the latest such position whose three bytes hash as p's do, (b)
+//              head16[1], the latest whose EIGHT bytes hash as p's do (12 bits of a 64-bit multiplicative hash; only positions with p + 8 <=
+//              n enter or look up), (c) p - 1; the fourth lane rests.  One farther back than 32 768 is refused by itself.  A barrier; then
+//              the position keeps the longest, the nearest on a tie, if it pays (the same test), and enters both tables by a max on half
+//              a word (positions + 1 fit 16 bits: two tables of 4 096 lie where head[] does).  A barrier.
+//     lazy     on the lengths of the WHOLE tile as find left them: len(i) > 0, i < 1 023 and len(i + 1) > len(i) flag position i; behind a
+//              barrier the flagged positions become literals (a rising chain gives way but for its last; never across two tiles)
+//   and the parse goes on as above: next(p) is still a function of p.
 //   codes      length-limited canonical codes (15 / 15 / 7 bits) of the literal-length, distance and code-length alphabets: a rank sort by
 //              all lanes, then lane 0: the in-place minimum-redundancy lengths of Moffat and Katajainen over the sorted weights, the
 //              limit by moving leaves down one level at a time until the Kraft sum fits, lengths handed out in sorted order
@@ -28,6 +38,7 @@
 //     sync()                        a barrier: what any lane wrote is visible to every lane behind it
 //     uni(v)                        v, known to be the same in every lane
 //     amax(p, v) aadd(p, v) aor(p, v) axor(p, v)   atomic max / add / or / xor on a word of Work
+//     amax16(a, i, v)               atomic max on a[i], half a word of Work (a: a 4-byte aligned array)
 //     excl_scan(a)                  a[0 .. TILE) becomes its exclusive prefix sum; returns the total (barriers inside)
 //     store16(dst, src)             16 bytes from Work to the member's slot
 #pragma once
@@ -41,7 +52,9 @@ enum { MAX_TEXT = 65280, TILE = 1024, HASH_BITS = 12, MIN_MATCH = 3, MAX_MATCH =
        SLACK = HEADER + 5 + TRAILER, // a member is never larger than its text + 31
        N_LIT = 288, N_DIST = 32, N_CL = 19, EOF_BYTES = 28,
        MATCH_BASE_BITS = 12,         // what a match is expected to cost in front of its extra bits: a length code of 7 and a distance code of 5
-       SURE_LENGTH = 32 };           // a match this long always pays: a literal costs a bit at least, a match 30 at most
+       SURE_LENGTH = 32,             // a match this long always pays: a literal costs a bit at least, a match 30 at most
+       SUB = 256 };                  // the dense mode looks a tile up, and enters it, in sub-tiles of this many positions
+enum { MODE_FAST = 0, MODE_DENSE = 1 }; // FAQCS_DEFLATE_FAST / FAQCS_DEFLATE_DENSE of include/faqcs_mi.h
 enum { KIND_STORED = 0, KIND_FIXED = 1, KIND_DYNAMIC = 2 };
 constexpr uint32_t NO_TOKEN = 0xffffffffu;
 
@@ -51,6 +64,7 @@ struct Work {
     uint32_t img[(MAX_TEXT + SLACK + 15) / 16 * 4]; // the member's image; in front of `place`, an inf::Tables for the CRC lies here
     union {
         uint32_t head[1 << HASH_BITS];           // find: position + 1 of the latest occurrence of a hash in the tiles in front, 0 = none
+        uint16_t head16[2][1 << HASH_BITS];      // the dense find (position + 1 <= 65 280): [0] by three bytes, [1] by eight, the sub-tiles in front
         struct {                                 // codes, choose, place
             uint32_t weight[N_LIT];
             uint16_t sorted[N_LIT];
@@ -59,7 +73,11 @@ struct Work {
         } c;
     } u;
     union {
-        struct { uint32_t match[TILE]; uint16_t next[2][TILE + 2]; uint8_t reach[TILE + 8]; } p; // parse
+        struct {                                 // parse
+            uint32_t match[TILE];
+            union { uint16_t next[2][TILE + 2]; uint32_t cand[3][SUB]; }; // (cand: the dense find's matches of a sub-tile, one row per candidate)
+            uint8_t reach[TILE + 8];             // (the dense mode keeps the lazy step's flags here until the parse starts)
+        } p;
         uint32_t bits[TILE];                     // place: the bit lengths of a tile's tokens, then their prefix
     } t;
     uint32_t byte_count[256];
@@ -87,6 +105,7 @@ DEF_HD uint32_t load32(const uint32_t *w, uint32_t i)
 DEF_HD uint32_t load8(const uint32_t *w, uint32_t i) { return (w[i >> 2] >> (8u * (i & 3u))) & 255u; }
 
 DEF_HD uint32_t hash3(uint32_t w) { return ((w & 0xffffffu) * 0x9e3779b1u) >> (32 - HASH_BITS); }
+DEF_HD uint32_t hash8(uint32_t lo, uint32_t hi) { return (uint32_t)((((uint64_t)hi << 32 | lo) * 0x9e3779b97f4a7c15ull) >> (64 - HASH_BITS)); }
 
 // how many bytes at p and at c < p agree, at most `most` (p + most <= the text's length): dwords, and the first differing byte by its bit
 DEF_HD uint32_t match_length(const uint32_t *text, uint32_t p, uint32_t c, uint32_t most)
@@ -121,6 +140,16 @@ DEF_HD uint32_t log2_eighths(uint32_t x)
 {
     const uint32_t e = msb(x);
     return 8 * e + ((e >= 3 ? x >> (e - 3) : x << (3 - e)) & 7u);
+}
+
+// does the match (len, dist) at p pay?  One under SURE_LENGTH bytes does when the literals it replaces are expected to cost more bits than it
+DEF_HD bool match_pays(const uint32_t *text, const uint16_t *lit_cost, uint32_t p, uint32_t len, uint32_t dist)
+{
+    uint32_t lc, le, lv, dc, de, dv, lits = 0;
+    length_symbol(len, lc, le, lv);
+    distance_symbol(dist, dc, de, dv);
+    for (uint32_t k = 0; k < len; ++k) lits += lit_cost[load8(text, p + k)];
+    return lits > 8 * (MATCH_BASE_BITS + le + de);
 }
 
 DEF_HD uint32_t fixed_lit_len(uint32_t s) { return s < 144 ? 8u : s < 256 ? 9u : s < 280 ? 7u : 8u; }
@@ -233,7 +262,7 @@ DEF_HD uint32_t token_bits(const Work &W, uint32_t tok, uint64_t &v)
 // One member: text[0 .. n) (1 <= n <= MAX_TEXT; any alignment, nothing outside it is read) -> slot[0 .. size rounded up to 16), a 16-byte
 // aligned buffer of the member's own of (n + SLACK) rounded up to 16 bytes.  tok: n rounded up to TILE words of scratch.  Returns the
 // member's size, bit 31 set when its block is a stored one (the same value in every lane).
-template <class X> DEF_HD uint32_t deflate_member(X &x, Work &W, const uint8_t *text, uint32_t n, uint32_t *tok, uint8_t *slot)
+template <int MODE = MODE_FAST, class X> DEF_HD uint32_t deflate_member(X &x, Work &W, const uint8_t *text, uint32_t n, uint32_t *tok, uint8_t *slot)
 {
     const uint32_t lane = x.lane(), nl = x.lanes();
     inf::Tables &T = *reinterpret_cast<inf::Tables *>(W.img);
@@ -278,6 +307,45 @@ template <class X> DEF_HD uint32_t deflate_member(X &x, Work &W, const uint8_t *
     const uint32_t n_tiles = (n + TILE - 1) / TILE;
     for (uint32_t t0 = 0; t0 < n_tiles * TILE; t0 += TILE) {
         const uint32_t entry = x.uni(W.entry);
+        if constexpr (MODE == MODE_DENSE) {
+        // find, sub-tile by sub-tile: four lanes per position, one candidate each (the fourth rests); then the position keeps the best of
+        // the three and enters both tables, which therefore hold exactly the positions in front of the sub-tile that is looked up
+        for (uint32_t s0 = 0; s0 < TILE; s0 += SUB) {
+            for (uint32_t j = lane; j < 4 * SUB; j += nl) {
+                const uint32_t i = j >> 2, c = j & 3u, p = t0 + s0 + i;
+                if (c == 3) continue;
+                uint32_t m = 0;
+                if (p >= entry && p + MIN_MATCH <= n) {
+                    uint32_t q = p; // the candidate's position + 1; (c) is p - 1
+                    if (c == 0) q = W.u.head16[0][hash3(load32(W.text, p))];
+                    else if (c == 1) q = p + 8 <= n ? W.u.head16[1][hash8(load32(W.text, p), load32(W.text, p + 4))] : 0u;
+                    if (q && p - (q - 1) <= MAX_DIST) m = match_length(W.text, p, q - 1, umin(MAX_MATCH, n - p)) << 16 | (p - (q - 1));
+                }
+                W.t.p.cand[c][i] = m;
+            }
+            x.sync();
+            for (uint32_t i = lane; i < SUB; i += nl) {
+                const uint32_t p = t0 + s0 + i;
+                uint32_t best = 0; // the longest, the nearest on a tie
+                for (uint32_t c = 0; c < 3; ++c) {
+                    const uint32_t m = W.t.p.cand[c][i];
+                    if ((m >> 16) > (best >> 16) || ((m >> 16) == (best >> 16) && (m & 0xffffu) < (best & 0xffffu))) best = m;
+                }
+                const uint32_t len = best >> 16;
+                if (len < MIN_MATCH || (len < SURE_LENGTH && !match_pays(W.text, W.lit_cost, p, len, best & 0xffffu))) best = 0;
+                W.t.p.match[s0 + i] = best;
+                if (p + MIN_MATCH <= n) x.amax16(W.u.head16[0], hash3(load32(W.text, p)), p + 1);
+                if (p + 8 <= n) x.amax16(W.u.head16[1], hash8(load32(W.text, p), load32(W.text, p + 4)), p + 1);
+            }
+            x.sync();
+        }
+        // the lazy step, on the tile's lengths as the find left them: a match gives way to a longer one at the next position of the tile
+        for (uint32_t i = lane; i < TILE; i += nl) {
+            const uint32_t len = W.t.p.match[i] >> 16;
+            W.t.p.reach[i] = (len && i + 1 < TILE && (W.t.p.match[i + 1] >> 16) > len) ? 1 : 0;
+        }
+        x.sync();
+        } else {
         // find
         for (uint32_t i = lane; i < TILE; i += nl) {
             const uint32_t p = t0 + i;
@@ -293,22 +361,18 @@ template <class X> DEF_HD uint32_t deflate_member(X &x, Work &W, const uint8_t *
                     const uint32_t l1 = match_length(W.text, p, p - 1, most);
                     if (l1 >= len) { len = l1; dist = 1; }
                 }
-                if (len >= MIN_MATCH && len < SURE_LENGTH) { // does it pay?
-                    uint32_t lc, le, lv, dc, de, dv, lits = 0;
-                    length_symbol(len, lc, le, lv);
-                    distance_symbol(dist, dc, de, dv);
-                    for (uint32_t k = 0; k < len; ++k) lits += W.lit_cost[load8(W.text, p + k)];
-                    if (lits <= 8 * (MATCH_BASE_BITS + le + de)) len = 0;
-                }
+                if (len >= MIN_MATCH && len < SURE_LENGTH && !match_pays(W.text, W.lit_cost, p, len, dist)) len = 0;
                 if (len < MIN_MATCH) len = dist = 0;
             }
             W.t.p.match[i] = len << 16 | dist;
         }
         x.sync();
-        // the tile enters head[]; the parse's first step
+        } // (MODE_FAST)
+        // the tile enters head[] (the dense mode's has, and its lazy step is applied instead); the parse's first step
         for (uint32_t i = lane; i < TILE; i += nl) {
             const uint32_t p = t0 + i;
-            if (p + MIN_MATCH <= n) x.amax(&W.u.head[hash3(load32(W.text, p))], p + 1);
+            if constexpr (MODE == MODE_DENSE) { if (W.t.p.reach[i]) W.t.p.match[i] = 0; }
+            else if (p + MIN_MATCH <= n) x.amax(&W.u.head[hash3(load32(W.text, p))], p + 1);
             const uint32_t len = W.t.p.match[i] >> 16;
             W.t.p.next[0][i] = (uint16_t)(p < n ? umin(i + (len ? len : 1u), TILE) : (uint32_t)TILE);
             W.t.p.reach[i] = (p == entry) ? 1 : 0;
@@ -486,6 +550,7 @@ struct HostExec {
     void sync() {}
     uint32_t uni(uint32_t v) const { return v; }
     void amax(uint32_t *p, uint32_t v) { if (v > *p) *p = v; }
+    void amax16(uint16_t *a, uint32_t i, uint32_t v) { if (v > a[i]) a[i] = (uint16_t)v; }
     void aadd(uint32_t *p, uint32_t v) { *p += v; }
     void aor(uint32_t *p, uint32_t v) { *p |= v; }
     void axor(uint32_t *p, uint32_t v) { *p ^= v; }

@@ -4,7 +4,8 @@
 //
 //   deflate_encode    ONE BLOCK PER MEMBER, members strided over the grid: the member's text, its image and every table in LDS (156 KB: one
 //                     block of 1 024 threads per compute unit); the tokens wait in 4 bytes per position of the block's own scratch; the
-//                     member leaves for its worst-case slot as 16-byte pieces, its size for sizes[]
+//                     member leaves for its worst-case slot as 16-byte pieces, its size for sizes[].  Two instantiations, the fast and the
+//                     dense match finder (FAQCS_DEFLATE_FAST / FAQCS_DEFLATE_DENSE); the launch picks by mode, everything behind it is shared
 //   deflate_sizes     one thread per member: block scan of the sizes, a tile sum per block
 //   scan_tile_sums    (faqcs_pack_common.h) one block: tile prefixes, the total, the overflow decision
 //   deflate_gather    one wave per member: slot -> comp at the member's position, whole 16-byte pieces between its unaligned ends;
@@ -59,6 +60,18 @@ struct BlockExec {
     __device__ __forceinline__ void sync() { __syncthreads(); }
     __device__ __forceinline__ uint32_t uni(uint32_t v) const { return uniu(v); }
     __device__ __forceinline__ void amax(uint32_t *p, uint32_t v) { atomicMax(p, v); }
+    // a max on half a word: compare-and-swap on the word that holds it, until the half is v at least (whatever the order, the largest stays)
+    __device__ __forceinline__ void amax16(uint16_t *a, uint32_t i, uint32_t v)
+    {
+        uint32_t *w = reinterpret_cast<uint32_t *>(a) + (i >> 1);
+        const uint32_t sh = 16u * (i & 1u);
+        uint32_t old = *w;
+        while (((old >> sh) & 0xffffu) < v) {
+            const uint32_t seen = atomicCAS(w, old, (old & ~(0xffffu << sh)) | v << sh);
+            if (seen == old) break;
+            old = seen;
+        }
+    }
     __device__ __forceinline__ void aadd(uint32_t *p, uint32_t v) { atomicAdd(p, v); }
     __device__ __forceinline__ void aor(uint32_t *p, uint32_t v) { atomicOr(p, v); }
     __device__ __forceinline__ void axor(uint32_t *p, uint32_t v) { atomicXor(p, v); }
@@ -73,6 +86,7 @@ struct BlockExec {
     __device__ __forceinline__ void store16(uint8_t *dst, const uint32_t *src) { *reinterpret_cast<uint4 *>(dst) = *reinterpret_cast<const uint4 *>(src); }
 };
 
+template <int MODE>
 __global__ __launch_bounds__(def::TILE) void deflate_encode(const uint8_t *__restrict__ text, const unsigned long long n_text, const uint32_t member_bytes, const uint32_t n_data,
                                                             uint32_t *__restrict__ tok, uint8_t *__restrict__ slots, uint32_t *__restrict__ sizes)
 {
@@ -84,7 +98,7 @@ __global__ __launch_bounds__(def::TILE) void deflate_encode(const uint8_t *__res
     for (uint32_t m = blockIdx.x; m < n_data; m += gridDim.x) {
         const unsigned long long a = (unsigned long long)m * member_bytes;
         const uint32_t n = (uint32_t)(n_text - a < member_bytes ? n_text - a : member_bytes); // (>= 1: m < n_data)
-        const uint32_t r = def::deflate_member(X, W, text + a, n, tok + (size_t)blockIdx.x * tok_words, slots + (size_t)m * slot);
+        const uint32_t r = def::deflate_member<MODE>(X, W, text + a, n, tok + (size_t)blockIdx.x * tok_words, slots + (size_t)m * slot);
         if (threadIdx.x == 0) sizes[m] = r;
     }
 }
@@ -146,7 +160,7 @@ __global__ __launch_bounds__(FINISH_THREADS) void deflate_finish(const uint32_t 
     }
 }
 
-unsigned long long g_lds_done = 0;
+unsigned long long g_lds_done[2] = {0, 0}; // (by mode)
 
 inline uint32_t encode_blocks(uint32_t n_data, int n_cu) { const uint32_t cap = (uint32_t)(n_cu > 0 ? n_cu : 256); return n_data < cap ? (n_data ? n_data : 1u) : cap; }
 
@@ -154,14 +168,15 @@ inline uint32_t encode_blocks(uint32_t n_data, int n_cu) { const uint32_t cap = 
 
 size_t faqcs_deflate_scratch_bytes(uint32_t n, uint32_t n_data, uint32_t member_bytes, int n_cu) { return carve(nullptr, n, n_data, member_bytes, encode_blocks(n_data, n_cu)).bytes; }
 
-hipError_t faqcs_launch_deflate_encode(const uint8_t *text, unsigned long long n_text, uint32_t member_bytes, uint32_t n, uint32_t n_data, void *scratch, int n_cu, hipStream_t st)
+hipError_t faqcs_launch_deflate_encode(const uint8_t *text, unsigned long long n_text, uint32_t member_bytes, uint32_t n, uint32_t n_data, int mode, void *scratch, int n_cu, hipStream_t st)
 {
     const uint32_t blocks = encode_blocks(n_data, n_cu);
     const Scratch s = carve(scratch, n, n_data, member_bytes, blocks);
     if (!n_data) return hipSuccess;
-    hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(deflate_encode), sizeof(def::Work), g_lds_done);
+    auto *kernel = mode == def::MODE_DENSE ? deflate_encode<def::MODE_DENSE> : deflate_encode<def::MODE_FAST>;
+    hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(kernel), sizeof(def::Work), g_lds_done[mode == def::MODE_DENSE]);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(deflate_encode, dim3(blocks), dim3(def::TILE), sizeof(def::Work), st, text, n_text, member_bytes, n_data, s.tok, s.slots, s.sizes);
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(def::TILE), sizeof(def::Work), st, text, n_text, member_bytes, n_data, s.tok, s.slots, s.sizes);
     return hipGetLastError();
 }
 

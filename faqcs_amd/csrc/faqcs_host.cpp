@@ -251,9 +251,10 @@ extern "C" int faqcs_inflate_host(const uint8_t *comp, uint64_t n_comp, const ui
     return 0;
 }
 
-int deflate_check_args(const char *who, const uint8_t *text, uint64_t n_text, uint32_t member_bytes, int final, const faqcs_deflate_out *out)
+int deflate_check_args(const char *who, const uint8_t *text, uint64_t n_text, uint32_t member_bytes, int final, int mode, const faqcs_deflate_out *out)
 {
     const std::string w(who);
+    if (mode != FAQCS_DEFLATE_FAST && mode != FAQCS_DEFLATE_DENSE) return fail(FAQCS_E_INVAL, w + ": the mode is FAQCS_DEFLATE_FAST or FAQCS_DEFLATE_DENSE");
     if (!out || !out->comp || !out->info) return fail(FAQCS_E_INVAL, w + ": null output, comp or info");
     if (!text && n_text) return fail(FAQCS_E_INVAL, w + ": null text");
     if ((uintptr_t)out->comp & 15u) return fail(FAQCS_E_INVAL, w + ": the output must be 16-byte aligned");
@@ -268,8 +269,14 @@ int deflate_check_args(const char *who, const uint8_t *text, uint64_t n_text, ui
 // a slot of its own, then -- when the total fits -- the members back to back, so that exactly comp[0 .. n_bytes) is written.
 extern "C" int faqcs_deflate_host(const uint8_t *text, uint64_t n_text, uint32_t member_bytes, int final, const faqcs_deflate_out *out)
 {
+    return faqcs_deflate_host_mode(text, n_text, member_bytes, final, FAQCS_DEFLATE_FAST, out);
+}
+
+extern "C" int faqcs_deflate_host_mode(const uint8_t *text, uint64_t n_text, uint32_t member_bytes, int final, int mode, const faqcs_deflate_out *out)
+{
     namespace def = faqcs_deflate;
-    if (int rc = deflate_check_args("faqcs_deflate_host", text, n_text, member_bytes, final, out)) return rc;
+    static_assert(FAQCS_DEFLATE_FAST == def::MODE_FAST && FAQCS_DEFLATE_DENSE == def::MODE_DENSE, "the encoder's modes are the header's");
+    if (int rc = deflate_check_args("faqcs_deflate_host", text, n_text, member_bytes, final, mode, out)) return rc;
     const uint32_t mb = member_bytes ? member_bytes : (uint32_t)def::MAX_TEXT;
     const uint32_t n_data = (uint32_t)((n_text + mb - 1) / mb), n = n_data + (final ? 1u : 0u);
     std::unique_ptr<def::Work> W(new def::Work);
@@ -281,7 +288,8 @@ extern "C" int faqcs_deflate_host(const uint8_t *text, uint64_t n_text, uint32_t
     for (uint32_t k = 0; k < n_data; ++k) {
         const uint64_t a = (uint64_t)k * mb;
         const uint32_t len = (uint32_t)std::min<uint64_t>(mb, n_text - a);
-        const uint32_t r = def::deflate_member(X, *W, text + a, len, tok.data(), slot.data());
+        const uint32_t r = mode == FAQCS_DEFLATE_DENSE ? def::deflate_member<def::MODE_DENSE>(X, *W, text + a, len, tok.data(), slot.data())
+                                                       : def::deflate_member<def::MODE_FAST>(X, *W, text + a, len, tok.data(), slot.data());
         info.n_stored += r >> 31;
         all.insert(all.end(), slot.begin(), slot.begin() + (r & 0x7fffffffu));
         ends[k] = (uint32_t)all.size();

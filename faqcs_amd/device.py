@@ -205,10 +205,11 @@ def inflated_text(engine, comp, member_offset=None, capacity=None):
     return o_text[a:a + n_bytes], o_off[:n_mem + 1]
 
 
-def deflated_bgzf(engine, text, member_bytes=0, final=True, capacity=None):
-    """`text` as BGZF members, compressed on the device (faqcs_deflate_device).
+def deflated_bgzf(engine, text, member_bytes=0, final=True, capacity=None, mode=capi.DEFLATE_FAST):
+    """`text` as BGZF members, compressed on the device (faqcs_deflate_device_mode).
 
     text: uint8 CUDA tensor (any alignment); member_bytes: text bytes per member (0: 65 280, as bgzip cuts); final: append the EOF member;
+    mode: capi.DEFLATE_FAST (the default) or capi.DEFLATE_DENSE, smaller members for more time;
     capacity: bytes to make room for (default: half the text, and the call is repeated once with what info asks for when that is too
     little).  Returns (comp, member_offset): uint8 [n_bytes], a view that starts 16-byte aligned, and int32 [n_members + 1] (bit pattern of
     uint32) -- with n_members = len(member_offset) - 1 the arguments faqcs_inflate_device takes."""
@@ -228,7 +229,7 @@ def deflated_bgzf(engine, text, member_bytes=0, final=True, capacity=None):
         shift = (-o_comp.data_ptr()) % 16
         out = capi.DeflateOut(o_comp.data_ptr() + shift, cap, o_off.data_ptr(), info.data_ptr())
         torch.cuda.current_stream(dev).synchronize()
-        engine.deflate_device(text.data_ptr() if n_text else None, n_text, int(member_bytes), final, out)
+        engine.deflate_device(text.data_ptr() if n_text else None, n_text, int(member_bytes), final, out, mode=mode)
         engine.sync()
         h = info.cpu().numpy()
         n_bytes, n_mem, overflow = int(h[0]), int(h[1]) & 0xFFFFFFFF, int(h[1]) >> 32

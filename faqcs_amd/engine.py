@@ -39,10 +39,10 @@ def bgzf_index_host(comp, final=True, lib=None):
     return off[:info.n_members + 1].copy(), int(info.consumed), int(info.error)
 
 
-def deflate_host(text, member_bytes=0, final=True, lib=None):
-    """faqcs_deflate_host (host only, no GPU): `text` (bytes or a uint8 array) as BGZF members of member_bytes bytes of text each (0: 65 280),
+def deflate_host(text, member_bytes=0, final=True, lib=None, mode=capi.DEFLATE_FAST):
+    """faqcs_deflate_host_mode (host only, no GPU; mode: capi.DEFLATE_FAST, what faqcs_deflate_host does, or capi.DEFLATE_DENSE): `text` (bytes or a uint8 array) as BGZF members of member_bytes bytes of text each (0: 65 280),
     the EOF member behind them when final.  Returns (comp bytes, member_offset uint32 [n_members + 1], n_stored): the bytes
-    faqcs_deflate_device produces for the same arguments."""
+    faqcs_deflate_device_mode produces for the same arguments."""
     lib = lib or capi.load_library()
     buf = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else np.ascontiguousarray(text, dtype=np.uint8)
     mb = int(member_bytes) or 65280
@@ -53,7 +53,7 @@ def deflate_host(text, member_bytes=0, final=True, lib=None):
     off = np.zeros(n + 1, dtype=np.uint32)
     info = capi.DeflateInfo()
     out = capi.DeflateOut(store.ctypes.data + shift, cap, off.ctypes.data, C.addressof(info))
-    _check(lib, lib.faqcs_deflate_host(buf.ctypes.data if len(buf) else None, len(buf), int(member_bytes), 1 if final else 0, C.byref(out)))
+    _check(lib, lib.faqcs_deflate_host_mode(buf.ctypes.data if len(buf) else None, len(buf), int(member_bytes), 1 if final else 0, int(mode), C.byref(out)))
     assert not info.overflow and info.n_members == n
     return store[shift:shift + info.n_bytes].tobytes(), off, int(info.n_stored)
 
@@ -160,11 +160,11 @@ class HipEngine:
         _check(self.lib, self.lib.faqcs_inflate_time_ms(self.ctx, C.byref(a), C.byref(g)))
         return a.value, g.value
 
-    def deflate_device(self, d_text, n_text, member_bytes, final, out):
-        """faqcs_deflate_device: text in device memory (d_text: device address, any alignment) -> BGZF members of member_bytes bytes of text
+    def deflate_device(self, d_text, n_text, member_bytes, final, out, mode=capi.DEFLATE_FAST):
+        """faqcs_deflate_device_mode (mode: capi.DEFLATE_FAST, what faqcs_deflate_device does, or capi.DEFLATE_DENSE): text in device memory (d_text: device address, any alignment) -> BGZF members of member_bytes bytes of text
         each (0: 65 280) in the arrays of `out` (a capi.DeflateOut of device pointers), the EOF member behind them when final.
         Enqueued; sync() waits."""
-        _check(self.lib, self.lib.faqcs_deflate_device(self.ctx, d_text, int(n_text), int(member_bytes), 1 if final else 0, C.byref(out)))
+        _check(self.lib, self.lib.faqcs_deflate_device_mode(self.ctx, d_text, int(n_text), int(member_bytes), 1 if final else 0, int(mode), C.byref(out)))
 
     def deflate_time_ms(self):
         """(encode ms, gather ms) of the last deflate_device() on this engine (HIP events on the compute stream); waits for it."""

@@ -542,6 +542,26 @@ typedef struct faqcs_deflate_out {
 int  faqcs_deflate_device(faqcs_ctx *ctx, const uint8_t *d_text, uint64_t n_text, uint32_t member_bytes, int final, const faqcs_deflate_out *out);
 int  faqcs_deflate_host(const uint8_t *text, uint64_t n_text, uint32_t member_bytes, int final, const faqcs_deflate_out *out);
 
+/* The same two calls with a choice of match finder.  FAQCS_DEFLATE_FAST is faqcs_deflate_device / faqcs_deflate_host, byte for byte.
+ * FAQCS_DEFLATE_DENSE spends more time on smaller members (zlib level 3 to 4 on FASTQ text).  Every rule above holds
+ * for it: the cutting, one block per member -- the smallest of dynamic, fixed and stored --, text + 31, final and the EOF member, overflow,
+ * the touched ranges, no alignment of d_text, device bytes == host bytes; the bytes are a function of (text, member_bytes, final, mode).
+ * The dense match finder, again without an order of execution:
+ *   - a 1 024-position tile of the member is looked up and entered in SUB-TILES of 256 positions, in order: the two tables a position sees
+ *     hold exactly the positions in front of its own sub-tile.
+ *   - the candidates of position p are (a) the latest of those positions whose three bytes have p's 12-bit hash, (b) the latest of them
+ *     whose EIGHT bytes have p's 12-bit hash (a 64-bit multiplicative hash; only positions with p + 8 <= the member's length enter this
+ *     table or look it up), (c) p - 1.  A candidate farther back than 32 768 is refused by itself; of the others the longest match wins,
+ *     the nearest on a tie; the test whether a match under 32 bytes pays is the fast mode's.
+ *   - the lazy step, inside a tile only: where position i < 1 023 of a tile keeps a match of length len(i) > 0 and len(i + 1) > len(i),
+ *     position i becomes a literal.  The rule is evaluated on the lengths as the find left them for the whole tile, so a rising chain
+ *     i, i + 1, i + 2 makes both i and i + 1 literals, and position 1 023 of a tile is never given up for position 0 of the next.
+ *   - the parse over the lengths that remain is the greedy one, as in the fast mode.
+ * FAQCS_E_INVAL in addition: a mode that is neither of the two (nothing is written). */
+enum { FAQCS_DEFLATE_FAST = 0, FAQCS_DEFLATE_DENSE = 1 };
+int  faqcs_deflate_device_mode(faqcs_ctx *ctx, const uint8_t *d_text, uint64_t n_text, uint32_t member_bytes, int final, int mode, const faqcs_deflate_out *out);
+int  faqcs_deflate_host_mode(const uint8_t *text, uint64_t n_text, uint32_t member_bytes, int final, int mode, const faqcs_deflate_out *out);
+
 /* Pipelined form of faqcs_submit(): returns a ticket; faqcs_wait(ticket) blocks until THAT batch's results have
  * landed in `results` (later batches may still be in flight: two input staging slots let the H2D copy of batch
  * k+1 overlap the kernels of batch k).  Host arenas / result arrays obtained from faqcs_host_alloc() are pinned,

@@ -1,9 +1,9 @@
 """A diagnostic, not a test: faqcs_deflate_device on 256 MiB of text (64 MiB distinct) of two kinds -- tools/inflate_bench.shaped_text and the
 Illumina-shaped text of tests/deflate_cases.py -- as medians of 7 HIP-event timings after a warm-up, beside a torch device-to-device copy of
 the text, one zlib thread at levels 1 and 6 in the same process, and the compressed size next to zlib's at level 1, level 6 and Huffman-only.
-Writes profiles/deflate/deflate_bench.json.
+Writes profiles/deflate/deflate_bench.json; with --mode dense (faqcs_deflate_device_mode, FAQCS_DEFLATE_DENSE) profiles/deflate/deflate_bench_dense.json.
 
-    python tools/deflate_bench.py [--mib 256] [--distinct-mib 64] [--out profiles/deflate/deflate_bench.json]
+    python tools/deflate_bench.py [--mode fast|dense] [--mib 256] [--distinct-mib 64] [--out profiles/deflate/deflate_bench.json]
 """
 import argparse
 import json
@@ -59,8 +59,11 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mib", type=int, default=256)
     ap.add_argument("--distinct-mib", type=int, default=64)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "deflate", "deflate_bench.json"))
+    ap.add_argument("--mode", choices=("fast", "dense"), default="fast")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "deflate", "deflate_bench.json" if a.mode == "fast" else "deflate_bench_dense.json")
+    mode = capi.DEFLATE_DENSE if a.mode == "dense" else capi.DEFLATE_FAST
     import torch
 
     import deflate_cases as dc
@@ -70,7 +73,7 @@ def main():
 
     dev = torch.device("cuda:0")
     eng = HipEngine(parse_args(["-u", "x", "-d", "y", "--ascii", "33"]), 256, 33, device=0)
-    result = {"device": torch.cuda.get_device_name(0), "mib": a.mib, "distinct_mib": a.distinct_mib, "texts": {}}
+    result = {"device": torch.cuda.get_device_name(0), "mib": a.mib, "distinct_mib": a.distinct_mib, "mode": a.mode, "texts": {}}
     reps = max(1, a.mib // a.distinct_mib)
     for name in ("shaped", "illumina"):
         distinct = shaped_text(a.distinct_mib << 20) if name == "shaped" else np.frombuffer(dc.illumina_text(a.distinct_mib << 20), np.uint8)
@@ -81,7 +84,7 @@ def main():
         torch.cuda.synchronize()
         enc, gat = [], []
         for rep in range(8):
-            eng.deflate_device(d_text.data_ptr(), n_text, 0, 1, out)
+            eng.deflate_device(d_text.data_ptr(), n_text, 0, 1, out, mode=mode)
             eng.sync()
             e, g = eng.deflate_time_ms()
             enc.append(e), gat.append(g)

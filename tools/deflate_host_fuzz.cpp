@@ -2,9 +2,10 @@
 // UBSan: generated texts of every shape and member size, every buffer of exactly the stated size on the heap (so that one byte too far is
 // an error), every member back through zlib's inflate and its CRC.
 //   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -o deflate_host_fuzz tools/deflate_host_fuzz.cpp -lz
-//   ./deflate_host_fuzz SEED N
+//   ./deflate_host_fuzz SEED N [dense]      (dense: the dense match finder, FAQCS_DEFLATE_DENSE, instead of the fast one)
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <memory>
 #include <random>
 #include <vector>
@@ -35,6 +36,7 @@ int main(int argc, char **argv)
 {
     const uint64_t seed = argc > 1 ? strtoull(argv[1], nullptr, 10) : 1;
     const int rounds = argc > 2 ? atoi(argv[2]) : 100;
+    const bool dense = argc > 3 && !strcmp(argv[3], "dense");
     std::mt19937_64 rng(seed);
     std::unique_ptr<def::Work> W(new def::Work);
     def::HostExec X;
@@ -49,7 +51,7 @@ int main(int argc, char **argv)
         std::unique_ptr<uint32_t[]> tok(new uint32_t[(n + def::TILE - 1) / def::TILE * def::TILE]);
         const uint32_t slot_bytes = (n + def::SLACK + 15u) & ~15u;
         uint8_t *slot = (uint8_t *)aligned_alloc(16, slot_bytes);
-        const uint32_t res = def::deflate_member(X, *W, in.get(), n, tok.get(), slot);
+        const uint32_t res = dense ? def::deflate_member<def::MODE_DENSE>(X, *W, in.get(), n, tok.get(), slot) : def::deflate_member(X, *W, in.get(), n, tok.get(), slot);
         const uint32_t size = res & 0x7fffffffu;
         if (size > n + def::SLACK || size < 26) { fprintf(stderr, "round %d: size %u for %u bytes\n", r, size, n); return 1; }
         if (faqcs_inflate::bgzf_member_size(slot, size) != size) { fprintf(stderr, "round %d: header\n", r); return 1; }
