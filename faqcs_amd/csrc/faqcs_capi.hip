@@ -322,7 +322,7 @@ static int enqueue_trim(faqcs_ctx *c, Timing &t, const Submission &s, const uint
     HIPCHK(hipEventRecord(t.a, c->compute));
     // the records of the launch BEFORE this one: this launch's blocks fold them when they run out of reads, if its kernel can (trim_lds with
     // a block of at least 122 KB of LDS: the 2x100 ... 2x150 variants); FAQCS_TAIL_FOLD=0: never (A/B)
-    static const bool tail_on = env_on("FAQCS_TAIL_FOLD");
+    const bool tail_on = env_on("FAQCS_TAIL_FOLD"); // (read at every submission, like FAQCS_TRIM_LONG below: a test runs one engine with it and one without)
     const bool offer_fold = c->pending_fold >= 0 && !c->pending_wide && tail_on;
     DevParams dp = c->dp;
     dp.fold_n = offer_fold ? c->pending_n : 0u;

@@ -67,6 +67,12 @@ __device__ __forceinline__ void lds_add_u32_quiet(uint32_t byte_offset, uint32_t
     asm volatile("ds_add_u32 %0, %1" : : "v"(byte_offset), "v"(v) : "memory");
 }
 __device__ __forceinline__ void lds_add_u32_quiet(uint32_t *cell, uint32_t v) { lds_add_u32_quiet((uint32_t)(size_t)(lds_u32_mut)cell, v); }
+// ... with a byte offset in the instruction's offset field (16 bits; a constant after unrolling, like bit_m1's bit), for the callers that add to a
+// row of cells from one address register
+__device__ __forceinline__ void lds_add_u32_quiet(uint32_t byte_offset, uint32_t v, const int imm_off)
+{
+    asm volatile("ds_add_u32 %0, %1 offset:%2" : : "v"(byte_offset), "v"(v), "n"(imm_off) : "memory");
+}
 template <int C, int J> struct BaseLookup {
     static __device__ __forceinline__ void run(const uint32_t t_base_lds, const uint32_t *ws, uint32_t two, uint32_t *inc)
     {
@@ -230,12 +236,98 @@ __device__ __forceinline__ void fs_acc_flush(FsAcc &f, const int lane, uint32_t 
     f = FsAcc();
 }
 
+// ---- (trim_lds) the six histogram adds of a chunk's epilogue, one read per lane.  64 lanes that add to ONE LDS address are serialised by the LDS
+// (110-250 clocks of the CU's LDS pipe for one instruction, against 3.4-4.8 with distinct banks: DESIGN 4, the instruction table), and that is the
+// common case: reads of one length, average qualities on a handful of values.  So the lanes of a wave are combined PER HISTOGRAM before they add:
+//   wave_value_count   lane L's count of the lanes whose value is L (values < 64: six ballots of the value's bits, lane L keeps the lanes that
+//                      agree with L in every bit): a histogram of up to 64 bins costs one add, its addresses distinct
+//   peel_pairs         up to four distinct keys, two per turn: the first remaining lane's key, a ballot of the lanes that share it, one add of their
+//                      count and one of their summed values by that lane; the two sums of a turn share ONE wave reduction (16-bit fields: 64 values of at most 1 023, which peel_pairs checks -- a larger value adds for itself).  Lanes left after that add for themselves.
+// Every add is a quiet one (above): both halves of the epilogue run beside an LDS-DMA in flight.  Adds of zero are dropped or kept freely.
+__device__ __forceinline__ uint32_t wave_value_count(const bool in, const uint32_t v, const int lane)
+{
+    unsigned long long b[7];
+    b[6] = __builtin_amdgcn_ballot_w64(in);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) b[k] = __builtin_amdgcn_ballot_w64(in && ((v >> k) & 1u) != 0u);
+    // One half of the wave after the other, one bit after the other (the empty asm pins the order): three registers at the kernel's register
+    // peak.  Left to itself the compiler forms all twelve b ^ keep terms first and ORs them together: eight registers, and a spill.
+    uint32_t cnt = 0;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        uint32_t m = (uint32_t)(b[6] >> (32 * h));
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+            m &= ~((uint32_t)(b[k] >> (32 * h)) ^ (uint32_t)bit_m1((uint32_t)lane, k)); // (bit k of the lane number set: b, else ~b; one v_bitop3)
+            asm volatile("" : "+v"(m));
+        }
+        cnt += (uint32_t)__popc(m);
+    }
+    return cnt;
+}
+// cnt_tab[key] += cnt_one per lane of `in`, sum_tab[key] += val (cnt_tab may be null: no counts).  Called by whole waves.
+// PRECONDITION: 64 x val < 2^16 (the two sums of a turn share one register).  Its callers pass a read length of a trim_lds variant with fewer than
+// 16 lanes per read (at most 152 bases; PEEL_MAX_VAL leaves room for every trim_lds length), and a value beyond the bound adds for itself.
+__device__ __forceinline__ void peel_pairs(const bool in, const uint32_t key, const uint32_t val, uint32_t *cnt_tab, const uint32_t cnt_one,
+                                           uint32_t *sum_tab, const int lane)
+{
+    constexpr uint32_t PEEL_MAX_VAL = 1023u;
+    static_assert(64u * PEEL_MAX_VAL < 65536u, "two sums of 64 values share one 32-bit register");
+    bool left = in && val <= PEEL_MAX_VAL;
+    const bool big = in && !left;
+    unsigned long long rem = __ballot(left);
+#pragma unroll 1
+    for (int turn = 0; turn < 2 && rem != 0ull; ++turn) {
+        const int f0 = __builtin_ctzll(rem);
+        const uint32_t k0 = (uint32_t)__builtin_amdgcn_readlane((int)key, f0);
+        const bool same0 = left && key == k0;
+        const unsigned long long b0 = __ballot(same0);
+        rem &= ~b0;
+        const int f1 = rem != 0ull ? __builtin_ctzll(rem) : f0; // (no second key: same1 is false everywhere)
+        const uint32_t k1 = (uint32_t)__builtin_amdgcn_readlane((int)key, f1);
+        const bool same1 = left && !same0 && key == k1;
+        const unsigned long long b1 = __ballot(same1);
+        rem &= ~b1;
+        const uint32_t s = (uint32_t)wave_sum_i32((int)((same0 ? val : 0u) | (same1 ? val << 16 : 0u)));
+        if (lane == f0) {
+            if (cnt_tab) lds_add_u32_quiet(cnt_tab + k0, (uint32_t)__popcll(b0) * cnt_one);
+            lds_add_u32_quiet(sum_tab + k0, s & 0xffffu);
+        }
+        if (same1 && lane == f1) {
+            if (cnt_tab) lds_add_u32_quiet(cnt_tab + k1, (uint32_t)__popcll(b1) * cnt_one);
+            lds_add_u32_quiet(sum_tab + k1, s >> 16);
+        }
+        left = left && !same0 && !same1;
+    }
+    if (left || big) {
+        if (cnt_tab) lds_add_u32_quiet(cnt_tab + key, cnt_one);
+        lds_add_u32_quiet(sum_tab + key, val);
+    }
+}
+// the length histogram: the lanes whose length is `cand` (wave-uniform: the length most of them are expected to have) in one add, the others for themselves
+__device__ __forceinline__ void len_hist_add(const bool in, const uint32_t len, const uint32_t cand, const uint32_t one, uint32_t *hlen, const int lane)
+{
+    const bool same = in && len == cand;
+    const unsigned long long b = __ballot(same);
+    if (b != 0ull && lane == __builtin_ctzll(b)) lds_add_u32_quiet(hlen + cand, (uint32_t)__popcll(b) * one);
+    if (in && !same) lds_add_u32_quiet(hlen + len, one);
+}
+#ifdef FAQCS_LDS_DIAG_EPI_NOCONFLICT // (diagnostic build, wrong results: the three adds of a lane on a cell no other lane adds to -- what the equal addresses of the epilogue's adds cost)
+__device__ __forceinline__ void epi_diag_adds(const bool in, const uint32_t v, uint32_t *hrq, uint32_t *hbq, const int lane)
+{
+    uint32_t *c = lane < FAQCS_NQ ? hrq + lane : hbq + (lane - FAQCS_NQ);
+    if (in) { lds_add_u32_quiet(c, 1u); lds_add_u32_quiet(c, 1u); lds_add_u32_quiet(c, v); }
+}
+#endif
+
 // (trim_lds) The half of the deferred epilogue that depends on nothing but the read's length and its pre-trim quality sum: the pre-trim
 // histogram cells and the FilterStat total.  A function of its own so that trim_lds can run it before the bases of the chunk are in LDS, while
-// their DMA is in flight (the LDS adds: lds_add_u32_quiet above); chunk_epilogue calls it itself unless it is told that the caller has (pre_done).
-// The lanes that share the first lane's (length, quality bin) pair are folded into ONE add per cell by that lane: 64 reads of one length are 64
-// adds to one LDS address otherwise, which the LDS serialises (~110 clocks per instruction, measured; equal-length reads with a narrow quality
-// spread are the common case).
+// their DMA is in flight; chunk_epilogue calls it itself unless it is told that the caller has (pre_done).  Called by whole waves.
+// The average-quality histogram is one wave_value_count (42 bins); a chunk of one length -- the common case -- adds its length once and its
+// bases per quality bin as count x length from the same counts; a chunk of several lengths sums them by peel_pairs.
+// COMBINE = false (the 16-lane variants: 32 or 20 reads per chunk, so the same work per chunk buys half as much or less -- 2x250 measured 41.69 -> 42.13 ms
+// per step with it, profiles/lds_same_address/ab_2x250_combined.txt): the lanes that share the first lane's (length, quality bin) pair add once, the others for themselves.
+template <bool COMBINE = true>
 __device__ __forceinline__ void chunk_epilogue_pre(const bool mine, const bool e_err, const uint32_t e_len, const int Vpre, const int lane, uint32_t *hlen,
                                                    uint32_t *hrq, uint32_t *hbqpre, const uint32_t *t_magic, FsAcc *defer)
 {
@@ -243,22 +335,43 @@ __device__ __forceinline__ void chunk_epilogue_pre(const bool mine, const bool e
         if (mine && e_len > 0 && Vpre > 0) qb_pre = e_len == 1 ? Vpre : (int)__umulhi((uint32_t)Vpre, t_magic[e_len]);
         qb_pre = qb_pre > 41 ? 41 : qb_pre;
         const bool act = mine && !e_err;
-        if (act) {
-            const uint32_t key = e_len | ((uint32_t)qb_pre << 16);
-            const bool same = key == (uint32_t)__builtin_amdgcn_readfirstlane((int)key);
-            const uint32_t cnt = (uint32_t)__builtin_popcountll(__ballot(same));
-            if (same) {
-                if (lane == __ffsll((unsigned long long)__ballot(true)) - 1) {
-                    lds_add_u32_quiet(hlen + e_len, cnt);
-                    lds_add_u32_quiet(hrq + qb_pre, cnt);
-                    if (e_len) lds_add_u32_quiet(hbqpre + qb_pre, cnt * e_len);
+#ifdef FAQCS_LDS_DIAG_EPI_NOCONFLICT
+        epi_diag_adds(act, e_len, hrq, hbqpre, lane);
+#else
+        const unsigned long long actm = COMBINE ? __ballot(act) : 0ull;
+        if (!COMBINE) { // (statement for statement what every variant did before per-histogram combining)
+            if (act) {
+                const uint32_t key = e_len | ((uint32_t)qb_pre << 16);
+                const bool same = key == (uint32_t)__builtin_amdgcn_readfirstlane((int)key);
+                const uint32_t cnt = (uint32_t)__builtin_popcountll(__ballot(same));
+                if (same) {
+                    if (lane == __ffsll((unsigned long long)__ballot(true)) - 1) {
+                        lds_add_u32_quiet(hlen + e_len, cnt);
+                        lds_add_u32_quiet(hrq + qb_pre, cnt);
+                        if (e_len) lds_add_u32_quiet(hbqpre + qb_pre, cnt * e_len);
+                    }
+                } else {
+                    lds_add_u32_quiet(hlen + e_len, 1u);
+                    lds_add_u32_quiet(hrq + qb_pre, 1u);
+                    if (e_len) lds_add_u32_quiet(hbqpre + qb_pre, e_len);
                 }
+            }
+        } else if (actm != 0ull) { // (wave-uniform)
+            const uint32_t len0 = (uint32_t)__builtin_amdgcn_readlane((int)e_len, __builtin_ctzll(actm));
+            const uint32_t cnt = wave_value_count(act, (uint32_t)qb_pre, lane); // (0 in the lanes from FAQCS_NQ on: no bin has their number)
+            // (bin = lane number, from a copy the compiler cannot see through: hrq + lane and hbqpre + lane would otherwise be hoisted out of the
+            // chunk loop and hold two registers for the whole kernel)
+            uint32_t bin = (uint32_t)lane;
+            asm volatile("" : "+v"(bin));
+            if (cnt) lds_add_u32_quiet(hrq + bin, cnt);
+            len_hist_add(act, e_len, len0, 1u, hlen, lane);
+            if (__ballot(act && e_len != len0) == 0ull) {
+                if (cnt && len0) lds_add_u32_quiet(hbqpre + bin, cnt * len0);
             } else {
-                lds_add_u32_quiet(hlen + e_len, 1u);
-                lds_add_u32_quiet(hrq + qb_pre, 1u);
-                if (e_len) lds_add_u32_quiet(hbqpre + qb_pre, e_len);
+                peel_pairs(act && e_len != 0u, (uint32_t)qb_pre, e_len, nullptr, 0u, hbqpre, lane);
             }
         }
+#endif
         const uint32_t one = 1u << 20;
         defer->tot += mine ? one | e_len : 0u;
 }
@@ -280,25 +393,37 @@ __device__ __forceinline__ void chunk_epilogue(const ReadOutcome &o, const bool 
         qb_pre = qb_pre > 41 ? 41 : qb_pre;
         qb_post = qb_post > 41 ? 41 : qb_post;
         if (defer) {
-            // (trim_lds) the same six histogram cells, equal ones of a chunk combined: the pre-trim three in chunk_epilogue_pre, here the post-trim three
-            if (!pre_done) chunk_epilogue_pre(mine, e_err, e_len, o.Vpre, lane, hlen, hrq, hbqpre, t_magic, defer);
-            const bool act = mine && !e_err;
-            if (act && e_ret) {
-                const uint32_t key = e_n | ((uint32_t)qb_post << 16);
-                const bool same = key == (uint32_t)__builtin_amdgcn_readfirstlane((int)key);
-                const uint32_t cnt = (uint32_t)__builtin_popcountll(__ballot(same));
-                if (same) {
-                    if (lane == __ffsll((unsigned long long)__ballot(true)) - 1) {
-                        lds_add_u32_quiet(hlen + e_n, cnt << 16);
-                        lds_add_u32_quiet(hrq + qb_post, cnt << 16);
-                        lds_add_u32_quiet(hbqpost + qb_post, cnt * e_n);
+            // (trim_lds) the same six histogram cells, the lanes of the wave combined per histogram: the pre-trim three in chunk_epilogue_pre, here the post-trim three
+            if (!pre_done) chunk_epilogue_pre<(LPR < 16)>(mine, e_err, e_len, o.Vpre, lane, hlen, hrq, hbqpre, t_magic, defer);
+            // post-trim: the average quality sits on two or three values (peel_pairs: the read count and the summed kept lengths of each), the kept
+            // length is spread except for the reads that keep every base (len_hist_add with the chunk's first length)
+            const bool pact = mine && !e_err && e_ret;
+#ifdef FAQCS_LDS_DIAG_EPI_NOCONFLICT
+            epi_diag_adds(pact, e_n, hrq, hbqpost, lane);
+#else
+            const unsigned long long pm = LPR < 16 ? __ballot(pact) : 0ull;
+            if (LPR >= 16) { // (as chunk_epilogue_pre<false>)
+                if (pact) {
+                    const uint32_t key = e_n | ((uint32_t)qb_post << 16);
+                    const bool same = key == (uint32_t)__builtin_amdgcn_readfirstlane((int)key);
+                    const uint32_t cnt = (uint32_t)__builtin_popcountll(__ballot(same));
+                    if (same) {
+                        if (lane == __ffsll((unsigned long long)__ballot(true)) - 1) {
+                            lds_add_u32_quiet(hlen + e_n, cnt << 16);
+                            lds_add_u32_quiet(hrq + qb_post, cnt << 16);
+                            lds_add_u32_quiet(hbqpost + qb_post, cnt * e_n);
+                        }
+                    } else {
+                        lds_add_u32_quiet(hlen + e_n, 0x10000u);
+                        lds_add_u32_quiet(hrq + qb_post, 0x10000u);
+                        lds_add_u32_quiet(hbqpost + qb_post, e_n);
                     }
-                } else {
-                    lds_add_u32_quiet(hlen + e_n, 0x10000u);
-                    lds_add_u32_quiet(hrq + qb_post, 0x10000u);
-                    lds_add_u32_quiet(hbqpost + qb_post, e_n);
                 }
+            } else if (pm != 0ull) { // (wave-uniform)
+                peel_pairs(pact, (uint32_t)qb_post, e_n, hrq, 0x10000u, hbqpost, lane);
+                len_hist_add(pact, e_n, (uint32_t)__builtin_amdgcn_readlane((int)e_len, __builtin_ctzll(pm)), 0x10000u, hlen, lane);
             }
+#endif
         } else if (!(o_dbg & 2u) && mine && !e_err) { // length and int(average quality) histograms (trim.cpp:254-258,539-543,877-885)
             atomicAdd(hlen + e_len, 1u);
             atomicAdd(hrq + qb_pre, 1u);
@@ -362,6 +487,56 @@ __device__ __forceinline__ void chunk_epilogue(const ReadOutcome &o, const bool 
 }
 
 #ifdef __HIPCC__
+// ---- one composition record per lane -> the block's 10 001 x 6 table of 16-bit cells (two per dword), the arithmetic of trim.cpp:860-874.  Called
+// by whole waves (the ballots below), by both fold kernels: composition_histogram (faqcs_trim_kernel.hip) and comp_fold_tail.  x (, y): the record
+// (WIDE: the two-word form, 11-bit fields), 0 = none; normt: the per-length factors in LDS.
+__device__ __forceinline__ void comp_cell_add(uint32_t *tab, const uint32_t e, const uint32_t v, const int lane)
+{
+#ifdef FAQCS_DIAG_FOLD_NOCONFLICT // (diagnostic build, wrong results: every lane of a wave on a dword of its own -- what the adds of a wave that meet on one cell or bank cost)
+    constexpr uint32_t ND_ = (FAQCS_NCOMP_BIN * FAQCS_NCOMP_KIND + 1) / 2;
+    uint32_t d = ((e >> 1) & ~63u) | (uint32_t)lane;
+    d = d >= ND_ ? d - 64u : d;
+    atomicAdd(&tab[d], v << (16 * (e & 1u)));
+#else
+    atomicAdd(&tab[e >> 1], v << (16 * (e & 1u)));
+#endif
+}
+template <bool WIDE>
+__device__ __forceinline__ void comp_fold_record(uint32_t *tab, const float *normt, const unsigned long long x, const unsigned long long y, const int lane)
+{
+    uint32_t nbin = 0xffffffffu; // this lane's N bin (none)
+    if (x & CR_VALID) {
+        uint32_t len, cnt[5];
+        if (WIDE) {
+            len = (uint32_t)(x & 2047u);
+            cnt[0] = (uint32_t)(x >> 11) & 2047u; cnt[1] = (uint32_t)(x >> 22) & 2047u; cnt[2] = (uint32_t)(x >> 33) & 2047u;
+            cnt[3] = (uint32_t)y & 2047u; cnt[4] = (uint32_t)(y >> 11) & 2047u;
+        } else {
+            len = (uint32_t)(x & 511u);
+#pragma unroll
+            for (int k = 0; k < 5; ++k) cnt[k] = (uint32_t)(x >> (9 + 9 * k)) & 511u;
+        }
+        const float norm = normt[len];
+        uint32_t idx[6];
+#pragma unroll
+        for (int k = 0; k < 5; ++k) idx[k] = (uint32_t)__fmul_rn(norm, (float)cnt[k]); // trim.cpp:862-872
+        idx[5] = idx[3] + idx[2];                                                      // :874 (G + C)
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+            if (k == 4) continue; // N: below
+            comp_cell_add(tab, idx[k] * FAQCS_NCOMP_KIND + k, 1u, lane);
+        }
+        nbin = idx[4] * FAQCS_NCOMP_KIND + 4;
+    }
+    // The N bin is the same for nearly every read (no N at all: bin 0): 64 lanes adding to ONE LDS address serialise, and
+    // that one kind cost more than the other five together.  The lanes of a wave that hit bin 0 add their count once; a read
+    // with N in it adds for itself (a loop over the distinct bins of the wave was measured: 3 % of the co-running trim launch).
+    constexpr uint32_t bin0 = 4u; // idx 0, kind 4
+    const unsigned long long zero = __ballot(nbin == bin0);
+    if (zero != 0ull && lane == __builtin_ctzll(zero)) atomicAdd(&tab[bin0 >> 1], (uint32_t)__popcll(zero) << (16 * (bin0 & 1u)));
+    if (nbin != 0xffffffffu && nbin != bin0) atomicAdd(&tab[nbin >> 1], 1u << (16 * (nbin & 1u)));
+}
+
 // ---- composition records -> the 10 001 x 6 composition tables (trim.cpp:860-874), by a block that owns >= 122 KB of LDS at address `tab` ----------
 // The arithmetic of composition_histogram (faqcs_trim_kernel.hip) with the records handed out dynamically: chunks of NT x 4 records from a
 // global counter, five chunks per claim.  Used by the blocks of a trim_lds launch that have run out of reads (round 6): `which` = 0 / 1 takes
@@ -411,31 +586,7 @@ __device__ __forceinline__ void comp_fold_tail(uint32_t *tab, const DevParams &P
 #pragma unroll
                 for (int u = 0; u < U; ++u) { const uint32_t i = c * CHUNK + (uint32_t)(u * NT + tid); x[u] = i < n ? rec[i] : 0ull; }
 #pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    uint32_t nbin = 0xffffffffu;
-                    if (x[u] & CR_VALID) {
-                        const uint32_t len = (uint32_t)(x[u] & 511u);
-                        uint32_t cnt[5];
-#pragma unroll
-                        for (int k = 0; k < 5; ++k) cnt[k] = (uint32_t)(x[u] >> (9 + 9 * k)) & 511u;
-                        const float norm = normt[len];
-                        uint32_t idx[6];
-#pragma unroll
-                        for (int k = 0; k < 5; ++k) idx[k] = (uint32_t)__fmul_rn(norm, (float)cnt[k]); // trim.cpp:862-872
-                        idx[5] = idx[3] + idx[2];                                                      // :874 (G + C)
-#pragma unroll
-                        for (int k = 0; k < 6; ++k) {
-                            if (k == 4) continue;
-                            const uint32_t e = idx[k] * FAQCS_NCOMP_KIND + k;
-                            atomicAdd(&tab[e >> 1], 1u << (16 * (e & 1u)));
-                        }
-                        nbin = idx[4] * FAQCS_NCOMP_KIND + 4;
-                    }
-                    constexpr uint32_t bin0 = 4u; // (no N at all: nearly every read -- one add per wave, as in composition_histogram)
-                    const unsigned long long zero = __ballot(nbin == bin0);
-                    if (zero != 0ull && (tid & 63) == __builtin_ctzll(zero)) atomicAdd(&tab[bin0 >> 1], (uint32_t)__popcll(zero) << (16 * (bin0 & 1u)));
-                    if (nbin != 0xffffffffu && nbin != bin0) atomicAdd(&tab[nbin >> 1], 1u << (16 * (nbin & 1u)));
-                }
+                for (int u = 0; u < U; ++u) comp_fold_record<false>(tab, normt, x[u], 0ull, tid & 63);
             }
             if (++since_flush == FLUSH_CLAIMS) {
                 __syncthreads();

@@ -640,42 +640,7 @@ __global__ __launch_bounds__(NT) void composition_histogram(const unsigned long 
             }
         }
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            uint32_t nbin = 0xffffffffu; // this thread's N bin (none)
-            if (x[u] & CR_VALID) {
-                uint32_t len, cnt[5];
-                if (WIDE) {
-                    len = (uint32_t)(x[u] & 2047u);
-                    cnt[0] = (uint32_t)(x[u] >> 11) & 2047u; cnt[1] = (uint32_t)(x[u] >> 22) & 2047u; cnt[2] = (uint32_t)(x[u] >> 33) & 2047u;
-                    cnt[3] = (uint32_t)y[u] & 2047u; cnt[4] = (uint32_t)(y[u] >> 11) & 2047u;
-                } else {
-                    len = (uint32_t)(x[u] & 511u);
-#pragma unroll
-                    for (int k = 0; k < 5; ++k) cnt[k] = (uint32_t)(x[u] >> (9 + 9 * k)) & 511u;
-                }
-                const float norm = normt[len];
-                uint32_t idx[6];
-#pragma unroll
-                for (int k = 0; k < 5; ++k) idx[k] = (uint32_t)__fmul_rn(norm, (float)cnt[k]); // :862-872
-                idx[5] = idx[3] + idx[2];                                                                                  // :874 (G + C)
-#pragma unroll
-                for (int k = 0; k < 6; ++k) {
-                    if (k == 4) continue; // N: below
-                    const uint32_t e = idx[k] * FAQCS_NCOMP_KIND + k;
-                    atomicAdd(&tab[e >> 1], 1u << (16 * (e & 1u)));
-                }
-                nbin = idx[4] * FAQCS_NCOMP_KIND + 4;
-            }
-            // The N bin is the same for nearly every read (no N at all: bin 0): 64 lanes adding to ONE LDS address serialise, and
-            // that one kind cost more than the other five together.  The lanes of a wave that hit bin 0 add their count once; a read
-            // with N in it adds for itself (a loop over the distinct bins of the wave was measured: 3 % of the co-running trim launch).
-            {
-                constexpr uint32_t bin0 = 4u; // idx 0, kind 4
-                const unsigned long long zero = __ballot(nbin == bin0);
-                if (zero != 0ull && (int)(threadIdx.x & 63u) == __builtin_ctzll(zero)) atomicAdd(&tab[bin0 >> 1], (uint32_t)__popcll(zero) << (16 * (bin0 & 1u)));
-                if (nbin != 0xffffffffu && nbin != bin0) atomicAdd(&tab[nbin >> 1], 1u << (16 * (nbin & 1u)));
-            }
-        }
+        for (int u = 0; u < U; ++u) comp_fold_record<WIDE>(tab, normt, x[u], y[u], tid & 63);
         if (((r + 1) % FLUSH_EVERY) == 0 || r + 1 == rounds) {
             __syncthreads();
             for (int d = tid; d < ND; d += NT) {

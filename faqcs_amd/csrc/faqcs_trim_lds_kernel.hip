@@ -518,7 +518,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void trim_lds(
 #pragma unroll
             for (int c = 0; c < FAQCS_NBASE; ++c) {
                 const uint32_t v = ((x >> sh_c[c]) & 63u) | (((y >> sh_c[c]) & 63u) << 16);
-                lds_add_u32_quiet(ad_c[c] + (uint32_t)(j * 4), v); // (quiet: the due spill of a chunk runs under the chunk's base DMA)
+                lds_add_u32_quiet(ad_c[c], v, j * 4); // (quiet: the due spill of a chunk runs under the chunk's base DMA; j in the instruction's offset field)
             }
             bpre[j] = 0; bpost[j] = 0;
         }
@@ -1227,7 +1227,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void trim_lds(
             // ---- under the base DMA: what needs neither the slot nor the bases.  The pre-trim half of the epilogue (the read's length and
             // V_pre are final), the register spill when one is due (accumulator cells and registers only), the words the S loop is handed.
             // Nothing here writes to a slot, and every LDS add is a quiet one (faqcs_trim_common.h): the compiler would drain the DMA in front of any other.
-            chunk_epilogue_pre(mine, read_err, v_len, V_pre, lane, smem + Cfg::O_LEN, smem + Cfg::O_RQ, smem + Cfg::O_BQPRE, smem + Cfg::O_TMAGIC, &fs_acc);
+            chunk_epilogue_pre<(LPR < 16)>(mine, read_err, v_len, V_pre, lane, smem + Cfg::O_LEN, smem + Cfg::O_RQ, smem + Cfg::O_BQPRE, smem + Cfg::O_TMAGIC, &fs_acc);
             if (++since_spill == REG_FLUSH_EVERY) { spill_base_regs(); since_spill = 0; } // (before this chunk's S pass: seven S passes between two spills, as ever)
             // i1: a | n << 8 | post << 16 | counted << 17 | chk << 18.  chk: the read fails the average quality but is still judged for
             // poly-N, which the reference tests first (trim.cpp:363-382).
