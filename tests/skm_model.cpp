@@ -1,6 +1,8 @@
 // skm_model.cpp -- host model of skm_extract / skm_combine's arithmetic (faqcs_amd/csrc/faqcs_kmer_skm_kernel.hip), built on the SAME
 // header the kernels use (faqcs_skm.h).  Test infrastructure: compiled and run by tests/test_skm_model.py (no GPU).
 //
+// (skm_model --file PATH: the reads of a file instead, see file_mode() -- tests/test_kmer_edges_model.py writes the catalogue of
+// tests/kmer_edges.py there.)
 // For random reads (N, lower case, repeats, windows, G -> N masks; 1 .. 700 bases; several k) it emulates a wave's extraction
 // rounds lane by lane -- the exchange rows are arrays -- and checks that
 //   * the k-mers of the items, expanded with SkmRoll, are exactly the canonical k-mers update_kmer() counts (trim.cpp:887-931:
@@ -294,8 +296,89 @@ static std::string revcomp(const std::string &s)
     return r;
 }
 
+// ---- file mode: skm_model --file PATH ------------------------------------------------------------------------------------------------
+// Every line is a read: <sequence in hex, or -> <a> <n> <k> <G -> N mask: one 0 / 1 per base, or ->.  Each goes through extract_read and,
+// where k = 31 and n <= 256, through extract_read16 as well, under the checks of the random mode; printed per read:
+//   <line> <k> <extract_read16: 1 deferred, 0 taken, -1 not tried> <k-mers of the longest item> <k-mers> <sum over the items of partition x k-mers>
+static int check_items(const std::vector<Item> &items, const std::string &s, const std::vector<uint8_t> &mask, int a, int n, const SkmGeom &g, uint32_t run,
+                       uint64_t total, std::map<u64, uint32_t> &part_of_key, long line, const char *who, uint32_t &longest, u64 &part_sum)
+{
+    std::vector<u64> got, want;
+    longest = 0; part_sum = 0;
+    for (const Item &it : items) {
+        const uint32_t nk = skm_item_kmers(it.y), part = skm_item_part(it.y);
+        if (nk > g.w || skm_item_run(it.y) != run) { fprintf(stderr, "line %ld (%s): item with %u k-mers (w = %u) / run field\n", line, who, nk, g.w); return 1; }
+        longest = std::max(longest, nk); part_sum += (u64)part * nk;
+        SkmRoll roll = skm_roll_begin(it.x, it.y, g);
+        for (uint32_t j = 0; j < nk; ++j) {
+            const u64 key = skm_roll_key(roll);
+            got.push_back(key);
+            auto f = part_of_key.find(key);
+            if (f == part_of_key.end()) part_of_key[key] = part;
+            else if (f->second != part) { fprintf(stderr, "line %ld (%s): key %llx in partitions %u and %u\n", line, who, key, f->second, part); return 1; }
+            skm_roll_next(roll, g);
+        }
+    }
+    reference_keys(s, mask, a, n, g, want);
+    if (total != want.size()) { fprintf(stderr, "line %ld (%s): total %llu != %zu\n", line, who, (u64)total, want.size()); return 1; }
+    std::sort(got.begin(), got.end());
+    std::sort(want.begin(), want.end());
+    if (got != want) { fprintf(stderr, "line %ld (%s): %zu keys from %zu items, want %zu\n", line, who, got.size(), items.size(), want.size()); return 1; }
+    return 0;
+}
+
+static int file_mode(const char *path)
+{
+    FILE *f = fopen(path, "r");
+    if (!f) { fprintf(stderr, "cannot open %s\n", path); return 1; }
+    std::map<uint32_t, std::map<u64, uint32_t>> part_of_key; // per k
+    std::vector<char> hex(1 << 16), msk(1 << 16);
+    int a, n, k;
+    long line = 0;
+    u64 n_keys = 0;
+    while (fscanf(f, "%65535s %d %d %d %65535s", hex.data(), &a, &n, &k, msk.data()) == 5) {
+        std::string s;
+        if (strcmp(hex.data(), "-") != 0)
+            for (size_t i = 0; hex[i] && hex[i + 1]; i += 2) { unsigned v = 0; sscanf(&hex[i], "%2x", &v); s.push_back((char)v); }
+        const size_t len = s.size();
+        if (k < 2 || k > 31 || a < 0 || n < 0 || (size_t)a + (size_t)n > len) { fprintf(stderr, "line %ld: bad a / n / k\n", line); return 1; }
+        s += "ACGTNACGTACGTTTTT"; // (whatever follows the read in the arena)
+        std::vector<uint8_t> mask(s.size() + 8, 0);
+        if (strcmp(msk.data(), "-") != 0) {
+            if (strlen(msk.data()) != len) { fprintf(stderr, "line %ld: the mask has %zu entries for %zu bases\n", line, strlen(msk.data()), len); return 1; }
+            for (size_t i = 0; i < len; ++i) mask[i] = msk[i] == '1';
+        }
+        const SkmGeom g = skm_geom((uint32_t)k);
+        const uint32_t run = (uint32_t)(line & 1023);
+        std::vector<Item> items;
+        uint64_t total = 0;
+        uint32_t longest = 0, longest16 = 0;
+        u64 part_sum = 0, part_sum16 = 0;
+        extract_read(s, mask, a, n, g, run, items, total);
+        if (check_items(items, s, mask, a, n, g, run, total, part_of_key[(uint32_t)k], line, "extract_read", longest, part_sum)) return 1;
+        int deferred = -1;
+        if (k == 31 && n <= 256) {
+            std::vector<Item> items16;
+            uint64_t total16 = 0;
+            deferred = extract_read16(s, mask, a, n, g, run, items16, total16) ? 0 : 1;
+            if (!deferred) {
+                if (check_items(items16, s, mask, a, n, g, run, total16, part_of_key[31], line, "extract_read16", longest16, part_sum16)) return 1;
+                if (part_sum16 != part_sum) { fprintf(stderr, "line %ld: the two kernels' partitions differ\n", line); return 1; }
+                longest = std::max(longest, longest16);
+            }
+        }
+        printf("%ld %d %d %u %llu %llu\n", line, k, deferred, longest, (u64)total, part_sum);
+        n_keys += total;
+        ++line;
+    }
+    fclose(f);
+    printf("ok: %ld reads, %llu k-mers\n", line, n_keys);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
+    if (argc > 2 && strcmp(argv[1], "--file") == 0) return file_mode(argv[2]);
     const int n_reads = argc > 1 ? atoi(argv[1]) : 3000;
     if (argc > 2) rng_state ^= strtoull(argv[2], nullptr, 0) * 0x9E3779B97F4A7C15ull;
     const uint32_t ks[] = {31, 31, 31, 2, 3, 5, 11, 15, 16, 17, 20, 25, 30};
