@@ -89,6 +89,18 @@ class PairInfo(C.Structure):
                 ("id_len", C.c_uint32 * 2), ("n_one_valid", C.c_uint32), ("n_none_valid", C.c_uint32)]
 
 
+class DetectInfo(C.Structure):
+    """faqcs_detect_info: the first decisive quality byte of a range of reads (33 / 64, or 0: none), the read that owns it, and whether the
+    range's first defline starts with "@NS"."""
+    _fields_ = [("quality_offset", C.c_int32), ("read", C.c_uint32), ("pos", C.c_uint32), ("byte", C.c_uint32), ("next_seq", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class ErrorInfo(C.Structure):
+    """faqcs_error_info: the reads in front of the first one with an F_ERR_* bit, and that read's error bits."""
+    _fields_ = [("n_good", C.c_uint32), ("flags", C.c_uint32)]
+
+
 ROUTE_V1, ROUTE_V2, ROUTE_NOWHERE = 1, 2, 0x80
 FILE_QC1, FILE_QC2, FILE_UNPAIRED, FILE_DISCARD = range(4)
 # the reference's names of the four files of a paired run, by FAQCS_FILE_* code
@@ -266,6 +278,11 @@ def load_library():
         "faqcs_finish": (i32, [vp, vp, u64]),
         "faqcs_reset_counters": (i32, [vp]),
         "faqcs_set_quality": (i32, [vp, i32]),
+        "faqcs_set_input_quality_offset": (i32, [vp, i32]),
+        "faqcs_detect_device": (i32, [vp, C.POINTER(Batch), u32, u32, vp, vp, vp, vp]),
+        "faqcs_detect_host": (i32, [C.POINTER(Batch), u32, u32, vp, vp, vp, vp]),
+        "faqcs_first_error_device": (i32, [vp, vp, u32, vp]),
+        "faqcs_first_error_host": (i32, [vp, u32, vp]),
         "faqcs_kmer_points": (i32, [vp, vp, u32, C.POINTER(u32)]),
         "faqcs_kmer_histogram": (i32, [vp, vp, vp, u64, C.POINTER(u64)]),
         "faqcs_kmer_totals": (i32, [vp, C.POINTER(u64), C.POINTER(u64)]),

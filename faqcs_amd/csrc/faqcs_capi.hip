@@ -19,13 +19,35 @@ static uint8_t na_to_bits_host(char c)
     return 0;
 }
 
+// the average-quality thresholds: per read length, the smallest V = sum(raw - offset) >= 0 for which NOT(ave_Q < avg); ave_Q per
+// trim.cpp:568-572.  (V < 0 gives ave_Q = 0 < avg, and V < table[len] is then true as well.)  The one table that depends on the input
+// quality offset: faqcs_set_input_quality_offset() builds it again.
+static void build_avgq(const faqcs_params &p, std::vector<int32_t> &avgq)
+{
+    const int N = FAQCS_TAB_LEN + 1;
+    avgq.assign(N, 0);
+    const volatile float avg = p.average_quality;
+    if (!(avg > 0.0f)) return;
+    for (int len = 1; len < N; ++len) {
+        auto pass = [&](int V) {
+            volatile float t = (float)(V + p.input_quality_offset * len) / (float)len;
+            volatile float v = t - (float)p.input_quality_offset;
+            const float a = v > 0.0f ? v : 0.0f;
+            return !(a < avg);
+        };
+        int lo = 0, hi = 256 * len;
+        if (!pass(hi)) avgq[len] = 0x7fffffff;
+        else { while (lo < hi) { const int mid = (lo + hi) >> 1; if (pass(mid)) hi = mid; else lo = mid + 1; } avgq[len] = lo; }
+    }
+}
+
 static void build_tables(const faqcs_params &p, std::vector<uint32_t> &lcthr, std::vector<int32_t> &avgq,
                          std::vector<float> &norm, std::vector<uint32_t> &magic, std::vector<uint32_t> &base)
 {
     const int N = FAQCS_TAB_LEN + 1;
-    lcthr.assign(N, 0xffffffffu); avgq.assign(N, 0); norm.assign(N, 0.f); magic.assign(N, 0);
+    lcthr.assign(N, 0xffffffffu); norm.assign(N, 0.f); magic.assign(N, 0);
+    build_avgq(p, avgq);
     const volatile float lc = p.low_complexity_cutoff_ratio;
-    const volatile float avg = p.average_quality;
     for (int len = 1; len < N; ++len) {
         uint32_t mono = 0xffff, di = 0xffff;
         volatile float nrm = (float)(1.0 / (double)len);                 // trim.cpp:483
@@ -35,19 +57,6 @@ static void build_tables(const faqcs_params &p, std::vector<uint32_t> &lcthr, st
         lcthr[len] = mono | (di << 16);
         norm[len] = (float)(FAQCS_NCOMP_BIN - 1) / (float)len;           // trim.cpp:860
         magic[len] = (uint32_t)((1ull << 32) / (uint64_t)len) + 1u;      // exact floor(V/len) for V < 2^16, len >= 2
-        if (avg > 0.0f) {
-            // smallest V = sum(raw - offset) >= 0 for which NOT(ave_Q < avg); ave_Q per trim.cpp:568-572.
-            // (V < 0 gives ave_Q = 0 < avg, and V < table[len] is then true as well.)
-            auto pass = [&](int V) {
-                volatile float t = (float)(V + p.input_quality_offset * len) / (float)len;
-                volatile float v = t - (float)p.input_quality_offset;
-                const float a = v > 0.0f ? v : 0.0f;
-                return !(a < avg);
-            };
-            int lo = 0, hi = 256 * len;
-            if (!pass(hi)) avgq[len] = 0x7fffffff;
-            else { while (lo < hi) { const int mid = (lo + hi) >> 1; if (pass(mid)) hi = mid; else lo = mid + 1; } avgq[len] = lo; }
-        }
     }
     // per input byte: 6-bit count fields in FaQCs enum order A,T,C,G,N (FaQCs.h:35-42), case-insensitive like
     // update_base_statistics (trim.cpp:831-857); flag bits for the case-sensitive tests (trim.cpp:396,586,1196)
@@ -229,7 +238,7 @@ extern "C" void faqcs_destroy(faqcs_ctx *c)
     for (auto &t : c->timings) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); (void)hipEventDestroy(t.p); (void)hipEventDestroy(t.k0); (void)hipEventDestroy(t.k1); }
     if (c->comm) comm_release(c->comm);
     if (c->comm_ev) (void)hipEventDestroy(c->comm_ev);
-    c->emit.release(); c->parse.release(); c->render.release(); c->pair.release(); c->render_pair.release(); c->inflate.release(); c->deflate.release();
+    c->emit.release(); c->parse.release(); c->render.release(); c->pair.release(); c->render_pair.release(); c->inflate.release(); c->deflate.release(); c->detect.release();
     if (c->ins_a) (void)hipEventDestroy(c->ins_a);
     if (c->ins_b) (void)hipEventDestroy(c->ins_b);
     for (int k = 0; k < 2; ++k) { if (c->fwd_free[k]) (void)hipEventDestroy(c->fwd_free[k]); if (c->fwd_copied[k]) (void)hipEventDestroy(c->fwd_copied[k]); c->fwd_items[k].release(); }
@@ -259,6 +268,23 @@ extern "C" int faqcs_set_quality(faqcs_ctx *c, int quality)
     if (quality < -93 || quality > 93) return fail(FAQCS_E_INVAL, "faqcs_set_quality: quality threshold outside [-93, 93]");
     c->prm.quality = quality;
     c->dp.Q = quality;
+    return 0;
+}
+
+// What faqcs_create() derives from the offset: prm, dp.in_off and the average-quality table.  The table is device memory that enqueued
+// kernels read, so the context's streams are drained first: work enqueued before the call sees the old offset, work after it the new one.
+extern "C" int faqcs_set_input_quality_offset(faqcs_ctx *c, int input_quality_offset)
+{
+    if (!c) return fail(FAQCS_E_INVAL, "null ctx");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->copy));
+    HIPCHK(hipStreamSynchronize(c->compute));
+    HIPCHK(hipStreamSynchronize(c->aux));
+    c->prm.input_quality_offset = input_quality_offset;
+    c->dp.in_off = input_quality_offset;
+    std::vector<int32_t> avgq;
+    build_avgq(c->prm, avgq);
+    HIPCHK(hipMemcpy(c->d_avgq, avgq.data(), avgq.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     return 0;
 }
 

@@ -1,5 +1,6 @@
 // faqcs_capi_seam.hip -- the device seams of the C ABI (include/faqcs_mi.h): faqcs_emit_device, faqcs_parse_device, faqcs_render_device,
-// faqcs_pair_device, faqcs_render_pair_device, faqcs_inflate_device and faqcs_deflate_device with their faqcs_*_time_ms.  Each is two stages of kernels between the marks of a
+// faqcs_pair_device, faqcs_render_pair_device, faqcs_inflate_device and faqcs_deflate_device with their faqcs_*_time_ms, and the untimed
+// faqcs_detect_device / faqcs_first_error_device.  Each of the timed ones is two stages of kernels between the marks of a
 // PackStage; the host statements of the same rules, and the argument checks shared with them, are in faqcs_host.cpp.
 #include "faqcs_ctx.h"
 #include "faqcs_deflate.h"
@@ -159,3 +160,23 @@ extern "C" int faqcs_deflate_device_mode(faqcs_ctx *c, const uint8_t *d_text, ui
 }
 
 extern "C" int faqcs_deflate_time_ms(faqcs_ctx *c, double *encode_ms, double *gather_ms) { return stage_times(c, &faqcs_ctx::deflate, "faqcs_deflate_time_ms: no deflate on this context yet", encode_ms, gather_ms); }
+
+// The decisions around trim(): a scan over the tiles and the finishing block.  Not a throughput stage: no marks, no faqcs_*_time_ms.
+extern "C" int faqcs_detect_device(faqcs_ctx *c, const faqcs_batch *b, uint32_t first, uint32_t count, const uint8_t *d_text, const uint32_t *d_def_pos,
+                                   const uint32_t *d_def_len, faqcs_detect_info *d_info)
+{
+    if (!c) return fail(FAQCS_E_INVAL, "null ctx");
+    if (int rc = detect_check_args("faqcs_detect_device", b, first, count, d_text, d_def_pos, d_def_len, d_info)) return rc;
+    if (int rc = c->detect.begin(c, faqcs_detect_scratch_bytes())) return rc;
+    HIPCHK(faqcs_launch_detect(b->qual, b->offset, first, count, d_text, d_def_pos, d_def_len, d_info, c->detect.scratch.p, c->n_cu, c->compute));
+    return 0;
+}
+
+extern "C" int faqcs_first_error_device(faqcs_ctx *c, const faqcs_read_result *d_results, uint32_t n, faqcs_error_info *d_info)
+{
+    if (!c) return fail(FAQCS_E_INVAL, "null ctx");
+    if (int rc = first_error_check_args("faqcs_first_error_device", d_results, n, d_info)) return rc;
+    if (int rc = c->detect.begin(c, faqcs_first_error_scratch_bytes(n))) return rc;
+    HIPCHK(faqcs_launch_first_error(d_results, n, d_info, c->detect.scratch.p, c->n_cu, c->compute));
+    return 0;
+}

@@ -1,6 +1,6 @@
 // faqcs_ctx.h -- internal to the host side of libfaqcs_mi.so (never installed): the context every entry point of include/faqcs_mi.h works
 // on, the launch functions of the kernel files, and the few host functions that cross the host side's translation units:
-//   faqcs_host.cpp       host statements and helpers without HIP (faqcs_host.h)     faqcs_capi_seam.hip  emit / parse / render / pair / inflate / deflate
+//   faqcs_host.cpp       host statements and helpers without HIP (faqcs_host.h)     faqcs_capi_seam.hip  emit / parse / render / pair / inflate / deflate / detect
 //   faqcs_capi.hip       create / destroy, submission, sync, counters, timing       faqcs_capi_comm.hip  RCCL
 //   faqcs_capi_kmer.hip  k-mer groups, the k-mer tails of a submission, faqcs_kmer_*
 // One faqcs_ctx == the (filter_stats, adapter_stats, PlotInfo, Options) quadruple the reference keeps in
@@ -83,6 +83,12 @@ hipError_t faqcs_launch_inflate_decode(const uint8_t *comp, const uint32_t *moff
 size_t faqcs_deflate_scratch_bytes(uint32_t n, uint32_t n_data, uint32_t member_bytes, int n_cu);
 hipError_t faqcs_launch_deflate_encode(const uint8_t *text, unsigned long long n_text, uint32_t member_bytes, uint32_t n, uint32_t n_data, int mode, void *scratch, int n_cu, hipStream_t st);
 hipError_t faqcs_launch_deflate_gather(uint32_t member_bytes, uint32_t n, uint32_t n_data, const faqcs_deflate_out *out, void *scratch, int n_cu, hipStream_t st);
+
+size_t faqcs_detect_scratch_bytes();
+size_t faqcs_first_error_scratch_bytes(uint32_t n);
+hipError_t faqcs_launch_detect(const uint8_t *qual, const uint32_t *off, uint32_t first, uint32_t count, const uint8_t *text, const uint32_t *def_pos,
+                               const uint32_t *def_len, faqcs_detect_info *info, void *scratch, int n_cu, hipStream_t st);
+hipError_t faqcs_launch_first_error(const faqcs_read_result *res, uint32_t n, faqcs_error_info *info, void *scratch, int n_cu, hipStream_t st);
 
 #define HIPCHK(x)                                                                                         \
     do {                                                                                                  \
@@ -172,6 +178,7 @@ struct faqcs_ctx {
     PackStage render_pair; // as render, over the 2 n_pairs candidates of the two mates | scan, gather
     PackStage inflate; // the header fields, the position and the status of every member, the scan's tile sums | scan, decode
     PackStage deflate; // every member's slot, size and position, a block's tokens, the scan's tile sums | encode, gather
+    PackStage detect;  // faqcs_detect_device and faqcs_first_error_device: the partial (first hit) of every tile | only the scratch is used: the stage is not timed
     // per-read composition records (trim kernel -> composition_histogram).  Two sets: the histogram kernels of
     // submission k run on the aux stream next to the trim kernel of submission k+1 (LDS-bound next to VALU-bound).
     struct RecSet { DevBuf<unsigned long long> pre, post; hipEvent_t trimmed = nullptr, folded = nullptr; bool used = false; };

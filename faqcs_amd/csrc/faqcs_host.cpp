@@ -491,3 +491,57 @@ extern "C" int faqcs_render_pair_host(const faqcs_params *p, int file, const faq
     }
     return 0;
 }
+
+// ---------------------------------------------------------------------------------------------------------
+// the decisions around trim() (include/faqcs_mi.h at faqcs_detect_device)
+// ---------------------------------------------------------------------------------------------------------
+int detect_check_args(const char *who, const faqcs_batch *b, uint32_t first, uint32_t count, const uint8_t *text, const uint32_t *def_pos, const uint32_t *def_len, const faqcs_detect_info *info)
+{
+    const std::string w(who);
+    if (!b || !info) return fail(FAQCS_E_INVAL, w + ": null batch or info");
+    if ((uint64_t)first + count > b->n_reads) return fail(FAQCS_E_INVAL, w + ": the range of reads leaves the batch");
+    if (count && (!b->qual || !b->offset)) return fail(FAQCS_E_INVAL, w + ": null batch arrays");
+    if ((text == nullptr) != (def_pos == nullptr) || (text == nullptr) != (def_len == nullptr)) return fail(FAQCS_E_INVAL, w + ": text, def_pos and def_len go together");
+    return 0;
+}
+
+int first_error_check_args(const char *who, const faqcs_read_result *results, uint32_t n, const faqcs_error_info *info)
+{
+    const std::string w(who);
+    if (!info) return fail(FAQCS_E_INVAL, w + ": null info");
+    if (n && !results) return fail(FAQCS_E_INVAL, w + ": null results");
+    return 0;
+}
+
+// The host statement of the detect rules: the bytes of the range in order (trim.cpp:599-617), then the first defline (trim.cpp:619-626).
+extern "C" int faqcs_detect_host(const faqcs_batch *b, uint32_t first, uint32_t count, const uint8_t *text, const uint32_t *def_pos, const uint32_t *def_len,
+                                 faqcs_detect_info *info)
+{
+    if (int rc = detect_check_args("faqcs_detect_host", b, first, count, text, def_pos, def_len, info)) return rc;
+    faqcs_detect_info d{0, first + count, 0u, 0u, 0u, 0u};
+    for (uint32_t i = first; i < first + count && !d.quality_offset; ++i)
+        for (uint32_t k = b->offset[i]; k < b->offset[i + 1]; ++k) {
+            const int c = (int)(int8_t)b->qual[k];
+            if (c > 74 || c < 59) {
+                d.quality_offset = c > 74 ? 64 : 33;
+                d.read = i; d.pos = k - b->offset[i]; d.byte = b->qual[k];
+                break;
+            }
+        }
+    if (count && text) d.next_seq = (def_len[first] >= 3 && memcmp(text + def_pos[first], "@NS", 3) == 0) ? 1u : 0u;
+    *info = d;
+    return 0;
+}
+
+// The host statement of where trim() threw: the results in order.
+extern "C" int faqcs_first_error_host(const faqcs_read_result *results, uint32_t n, faqcs_error_info *info)
+{
+    if (int rc = first_error_check_args("faqcs_first_error_host", results, n, info)) return rc;
+    faqcs_error_info e{n, 0u};
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t f = results[i].flags & (FAQCS_F_ERR_QUALITY | FAQCS_F_ERR_BASE);
+        if (f) { e.n_good = i; e.flags = f; break; }
+    }
+    *info = e;
+    return 0;
+}

@@ -18,3 +18,5 @@ FAQCS_HIDDEN int inflate_check_args(const char *who, const uint8_t *comp, uint64
 FAQCS_HIDDEN int deflate_check_args(const char *who, const uint8_t *text, uint64_t n_text, uint32_t member_bytes, int final, int mode, const faqcs_deflate_out *out);
 FAQCS_HIDDEN int pair_check_args(const char *who, const faqcs_mate *m1, const faqcs_mate *m2, const uint8_t *route, const faqcs_pair_info *info, uint32_t *n);
 FAQCS_HIDDEN int render_pair_check_args(const char *who, int file, const faqcs_mate *m1, const faqcs_mate *m2, const uint8_t *route, uint32_t n_pairs, const faqcs_render_out *out);
+FAQCS_HIDDEN int detect_check_args(const char *who, const faqcs_batch *b, uint32_t first, uint32_t count, const uint8_t *text, const uint32_t *def_pos, const uint32_t *def_len, const faqcs_detect_info *info);
+FAQCS_HIDDEN int first_error_check_args(const char *who, const faqcs_read_result *results, uint32_t n, const faqcs_error_info *info);

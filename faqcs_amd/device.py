@@ -1,6 +1,6 @@
 """Torch-facing helpers of the device seam: inputs and outputs are torch tensors that live on the GPU; the work is the
 library's HIP kernels (faqcs_emit_device, faqcs_render_device, faqcs_pair_device, faqcs_render_pair_device, faqcs_inflate_device,
-faqcs_deflate_device), never torch ops."""
+faqcs_deflate_device, faqcs_detect_device), never torch ops."""
 import ctypes as C
 
 from . import _capi as capi
@@ -101,6 +101,33 @@ class DeviceMate:
                       self.def_pos.data_ptr(), self.def_len.data_ptr())
         m._batch = b
         return m
+
+
+def first_buffer_decisions(engine, mate1, mate2=None, first=0, count=None):
+    """The decisions the reference takes on its first buffer, for device-resident mates (DeviceMate each; faqcs_detect_device): the
+    quality-offset auto-detect and the NextSeq look at the first defline over reads [first, first + count) of each mate (count None: up
+    to capi.SEGMENT_READS reads, the reference's buffer).  Only the infos come back to the host.  Returns the dict of the
+    faqcs_detect_info fields of mate1, or a tuple of two dicts when mate2 is given (the caller compares the two verdicts: the reference
+    stops with "Inconsistent quality offset detection between reads one and two")."""
+    import torch
+
+    mates = [m for m in (mate1, mate2) if m is not None]
+    dev = mate1.text.device
+    d_info = torch.zeros((len(mates), 6), dtype=torch.int32, device=dev)
+    torch.cuda.current_stream(dev).synchronize()  # the library's compute stream is its own: the inputs must be complete
+    keep = []
+    for k, m in enumerate(mates):
+        c = max(0, min(m.n - first, capi.SEGMENT_READS)) if count is None else int(count)
+        cm = m.capi()
+        keep.append(cm)
+        engine.detect_device(cm._batch, first, c, d_info[k].data_ptr(), m.text.data_ptr(), m.def_pos.data_ptr(), m.def_len.data_ptr())
+    engine.sync()
+    h = d_info.cpu().numpy()
+    out = []
+    for k in range(len(mates)):
+        p = capi.DetectInfo.from_buffer_copy(h[k].tobytes())
+        out.append({f: int(getattr(p, f)) for f, _ in capi.DetectInfo._fields_})
+    return out[0] if mate2 is None else tuple(out)
 
 
 def pair_route(engine, mate1, mate2):

@@ -318,6 +318,39 @@ def render_pair_model(opt, in_off, file, mate1, mate2, route, n_pairs):
     return np.frombuffer(b"".join(pieces), dtype=np.uint8), np.asarray(ends, dtype=np.uint32), np.asarray(index, dtype=np.uint32)
 
 
+def detect_model(qual, offset, first, count, text=None, def_pos=None, def_len=None):
+    """The rules of faqcs_detect_device / faqcs_detect_host (include/faqcs_mi.h) in numpy: the lowest arena position b in
+    [offset[first], offset[first + count]) whose quality byte, as a signed char, is > 74 (64) or < 59 (33); the read that owns it; and
+    whether the defline content of read `first` starts with "@NS" (trim.cpp:599-626).  -> dict of the faqcs_detect_info fields."""
+    offset = np.asarray(offset, dtype=np.int64)
+    first, count = int(first), int(count)
+    if first + count > len(offset) - 1:
+        raise ValueError("the range of reads leaves the batch")
+    if len({text is None, def_pos is None, def_len is None}) != 1:
+        raise ValueError("text, def_pos and def_len go together")
+    d = dict(quality_offset=0, read=first + count, pos=0, byte=0, next_seq=0, reserved=0)
+    if count:
+        a, e = int(offset[first]), int(offset[first + count])
+        q = np.asarray(qual, dtype=np.uint8)[a:e].view(np.int8)
+        hit = np.nonzero((q > 74) | (q < 59))[0]
+        if len(hit):
+            b = a + int(hit[0])
+            read = int(np.searchsorted(offset[first:first + count + 1], b, side="right")) - 1 + first  # the last i with offset[i] <= b
+            d.update(quality_offset=64 if q[hit[0]] > 74 else 33, read=read, pos=b - int(offset[read]), byte=int(q[hit[0]]) & 0xFF)
+        if text is not None:
+            p, ln = int(def_pos[first]), int(def_len[first])
+            d["next_seq"] = int(ln >= 3 and bytes(bytearray(text[p:p + 3])) == b"@NS")
+    return d
+
+
+def first_error_model(res):
+    """The rule of faqcs_first_error_device / faqcs_first_error_host in numpy: (n_good, flags) -- the index of the first result with an
+    F_ERR_* bit, or len(res), and that read's two error bits."""
+    f = np.asarray(res["flags"], dtype=np.uint16) & np.uint16(capi.F_ERR_QUALITY | capi.F_ERR_BASE)
+    hit = np.nonzero(f)[0]
+    return (int(hit[0]), int(f[hit[0]])) if len(hit) else (len(f), 0)
+
+
 class Run:
     """State the reference keeps in main(): filter_stats, adapter_stats, PlotInfo, Options (FaQCs.cpp:67-69)."""
 

@@ -58,6 +58,41 @@ def deflate_host(text, member_bytes=0, final=True, lib=None, mode=capi.DEFLATE_F
     return store[shift:shift + info.n_bytes].tobytes(), off, int(info.n_stored)
 
 
+def detect_host(qual, offset, first=0, count=None, text=None, def_pos=None, def_len=None, lib=None):
+    """faqcs_detect_host (host only, no GPU): the first decisive quality byte of reads [first, first + count) of a packed batch (qual: uint8
+    arena, offset: uint32 [n + 1]; count None: to the batch's end) and, with text / def_pos / def_len (all three or none), whether the
+    defline of read `first` starts with "@NS".  Returns the faqcs_detect_info fields as a dict."""
+    lib = lib or capi.load_library()
+    qual = np.ascontiguousarray(qual, dtype=np.uint8)
+    qual = qual if len(qual) else np.zeros(1, np.uint8)
+    offset = np.ascontiguousarray(offset, dtype=np.uint32)
+    n = len(offset) - 1
+    count = n - first if count is None else count
+    given = [x is not None for x in (text, def_pos, def_len)]
+    if text is not None:
+        text = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else np.ascontiguousarray(text, dtype=np.uint8)
+        text = text if len(text) else np.zeros(1, np.uint8)
+    if def_pos is not None:
+        def_pos = np.ascontiguousarray(np.append(def_pos, 0), dtype=np.uint32)
+    if def_len is not None:
+        def_len = np.ascontiguousarray(np.append(def_len, 0), dtype=np.uint32)
+    b = capi.Batch(None, qual.ctypes.data, offset.ctypes.data, n, 0, None, 0, None)
+    info = capi.DetectInfo()
+    _check(lib, lib.faqcs_detect_host(C.byref(b), int(first), int(count), text.ctypes.data if given[0] else None,
+                                      def_pos.ctypes.data if given[1] else None, def_len.ctypes.data if given[2] else None, C.byref(info)))
+    return {f: int(getattr(info, f)) for f, _ in capi.DetectInfo._fields_}
+
+
+def first_error_host(results, lib=None):
+    """faqcs_first_error_host (host only, no GPU): (n_good, flags) of a per-read result array (capi.RESULT_DTYPE) -- the index of the first
+    read with an F_ERR_* bit, or len(results), and that read's error bits."""
+    lib = lib or capi.load_library()
+    results = np.ascontiguousarray(results, dtype=capi.RESULT_DTYPE)
+    info = capi.ErrorInfo()
+    _check(lib, lib.faqcs_first_error_host(results.ctypes.data if len(results) else None, len(results), C.byref(info)))
+    return int(info.n_good), int(info.flags)
+
+
 class HipEngine:
     name = "hip"
 
@@ -178,6 +213,23 @@ class HipEngine:
 
     def set_quality(self, q):
         _check(self.lib, self.lib.faqcs_set_quality(self.ctx, int(q)))
+
+    def set_input_quality_offset(self, offset):
+        """faqcs_set_input_quality_offset: the input quality offset of every LATER submission, emission and rendering (what auto-detection
+        found).  Waits for the work enqueued so far, which keeps the old offset."""
+        _check(self.lib, self.lib.faqcs_set_input_quality_offset(self.ctx, int(offset)))
+        self.holder.p.input_quality_offset = int(offset)
+
+    def detect_device(self, batch, first, count, d_info, d_text=None, d_def_pos=None, d_def_len=None):
+        """faqcs_detect_device: the first decisive quality byte of reads [first, first + count) of a device-resident batch (a capi.Batch of
+        device pointers; only qual, offset and n_reads are read) and, with d_text / d_def_pos / d_def_len (all three or none), whether the
+        defline of read `first` starts with "@NS", into d_info (a faqcs_detect_info in device memory).  Enqueued; sync() waits."""
+        _check(self.lib, self.lib.faqcs_detect_device(self.ctx, C.byref(batch), int(first), int(count), d_text, d_def_pos, d_def_len, d_info))
+
+    def first_error_device(self, d_results, n, d_info):
+        """faqcs_first_error_device: the first of n device results with an F_ERR_* bit into d_info (a faqcs_error_info in device memory).
+        Enqueued behind the submission that fills d_results; sync() waits."""
+        _check(self.lib, self.lib.faqcs_first_error_device(self.ctx, d_results, int(n), d_info))
 
     def sync(self):
         _check(self.lib, self.lib.faqcs_sync(self.ctx))

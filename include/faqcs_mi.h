@@ -36,7 +36,8 @@ extern "C" {
  * faqcs_parse_device / faqcs_parse_host (FASTQ text to a packed batch) and faqcs_render_device / faqcs_render_host (the FASTQ text of the
  * output files), and faqcs_inflate_device / faqcs_inflate_host / faqcs_bgzf_index_host (BGZF members to that text),
  * and faqcs_deflate_device / faqcs_deflate_host (text to BGZF members), and faqcs_pair_device / faqcs_pair_host /
- * faqcs_render_pair_device / faqcs_render_pair_host (the two mates of a paired run from two batches). */
+ * faqcs_render_pair_device / faqcs_render_pair_host (the two mates of a paired run from two batches), and faqcs_detect_device /
+ * faqcs_detect_host / faqcs_first_error_device / faqcs_first_error_host / faqcs_set_input_quality_offset (the decisions around trim()). */
 #define FAQCS_ABI_VERSION 2
 
 /* FilterStat enum order, FaQCs.h:46-75 */
@@ -562,6 +563,61 @@ enum { FAQCS_DEFLATE_FAST = 0, FAQCS_DEFLATE_DENSE = 1 };
 int  faqcs_deflate_device_mode(faqcs_ctx *ctx, const uint8_t *d_text, uint64_t n_text, uint32_t member_bytes, int final, int mode, const faqcs_deflate_out *out);
 int  faqcs_deflate_host_mode(const uint8_t *text, uint64_t n_text, uint32_t member_bytes, int final, int mode, const faqcs_deflate_out *out);
 
+/* The decisions the reference's driver takes AROUND trim(), for a caller whose reads are in device memory: each is the FIRST element of a
+ * contiguous range for which a predicate holds, in input order as everywhere in the seam, and each brings back a few bytes of info.
+ *
+ * faqcs_detect_device / faqcs_detect_host: the quality-offset auto-detect (auto_detect_quality_offset, trim.cpp:599-617, called at
+ * FaQCs.cpp:261-270, 393-402, 609-611, 669-671; the reference's default: options.cpp:122) and the look of the NextSeq check at the first
+ * defline (auto_detect_next_seq, trim.cpp:619-626, called at FaQCs.cpp:272-277, 404-414).
+ *   - the range.  The reference decides on ONE buffer: the first full one of FAQCS_SEGMENT_READS reads, or the last partial one at the end
+ *     of the input.  A device chunk holds more or fewer reads than that, so the call takes the reads [first, first + count) of the batch;
+ *     the caller keeps the budget and calls again on the next chunk while undecided and under FAQCS_SEGMENT_READS reads.
+ *     first + count > batch->n_reads is FAQCS_E_INVAL.  count == 0 yields {0, first, 0, 0, 0, 0}.
+ *   - the offset.  Reads are packed back to back, so "the first decisive byte in read order" is the lowest b in
+ *     [offset[first], offset[first + count]) whose qual[b], read as a SIGNED char, is > 74 or < 59.  > 74 gives 64, < 59 gives 33; the
+ *     bytes 0x80 ... 0xff are therefore 33.  read is the unique i with offset[i] <= b < offset[i + 1] (a read of length 0 never owns a
+ *     byte), pos = b - offset[read], byte = qual[b].  Without such a byte quality_offset = 0 -- the reference throws "Unknown quality
+ *     format!" --, read = first + count and pos = byte = 0.
+ *   - only batch->qual, batch->offset and batch->n_reads are read; seq, segment_start and terminal_n may be NULL.  The padding contract of
+ *     faqcs_batch holds for the device form: whole aligned 16-byte vectors are loaded over both ends of the range.  Bytes outside the
+ *     range are never interpreted.
+ *   - NextSeq.  text, def_pos and def_len (what faqcs_parse_device delivered) are all given or all NULL; anything else is FAQCS_E_INVAL.
+ *     With them next_seq = count > 0 && def_len[first] >= 3 && text[def_pos[first] .. + 3) == "@NS" -- the defline content includes the
+ *     '@', as Read::def does --, without them 0.  The comparison with -q, the bump (faqcs_set_quality) and the message stay with the caller.
+ *   FAQCS_E_INVAL in addition: a null ctx / batch / info, a null batch->qual or batch->offset with count > 0.
+ *
+ * faqcs_first_error_device / faqcs_first_error_host: where trim() threw (FAQCS_F_ERR_QUALITY: fastq.h:31-33, FAQCS_F_ERR_BASE:
+ * seq_overlap.cpp:409; the reference stops before the buffer that holds such a read, FaQCs.cpp:287-361).  n_good is the lowest i < n with
+ * results[i].flags & (FAQCS_F_ERR_QUALITY | FAQCS_F_ERR_BASE) and flags holds that read's two error bits; without such a read the result
+ * is {n, 0}, and n == 0 yields {0, 0}.  Mapping n_good to the caller's FAQCS_SEGMENT_READS-read buffers is host arithmetic on its own
+ * segment_start.  FAQCS_E_INVAL: a null ctx / info, null results with n > 0.
+ *
+ * The device forms: every pointer but ctx and batch is a DEVICE pointer (batch->qual / offset too, as for faqcs_submit_device; d_info
+ * included).  They are enqueued on the context's compute stream and return at once -- so they run behind the parse or the submission that
+ * produced their input --; faqcs_sync() waits.  info is ALWAYS complete and nothing but info is written.  Its bytes are a function of the
+ * inputs alone: no atomics, a partial per 16 KB tile and one finishing block, as in the pair stage.  They take no parameter from the
+ * context.  Scratch (4 bytes per tile; the byte form's for the 2^32 bytes that 32-bit offsets can span, 1 MB) is the library's: grown on
+ * demand, freed by faqcs_destroy().  The host forms are the host statements of these rules: plain single-threaded C++, no HIP call, no
+ * padding needed. */
+typedef struct faqcs_detect_info {
+    int32_t  quality_offset;  /* 33, 64, or 0: no decisive byte in the range (the reference throws "Unknown quality format!") */
+    uint32_t read;            /* batch index of the read that holds the decisive byte; first + count when there is none */
+    uint32_t pos;             /* its position inside that read; 0 when none */
+    uint32_t byte;            /* the raw byte; 0 when none */
+    uint32_t next_seq;        /* 1: count > 0, deflines were given and the defline content of read `first` starts with "@NS" */
+    uint32_t reserved;        /* 0 */
+} faqcs_detect_info;
+
+int  faqcs_detect_device(faqcs_ctx *ctx, const faqcs_batch *batch, uint32_t first, uint32_t count,
+                         const uint8_t *d_text, const uint32_t *d_def_pos, const uint32_t *d_def_len,
+                         faqcs_detect_info *d_info);
+int  faqcs_detect_host(const faqcs_batch *batch, uint32_t first, uint32_t count,
+                       const uint8_t *text, const uint32_t *def_pos, const uint32_t *def_len, faqcs_detect_info *info);
+
+typedef struct faqcs_error_info { uint32_t n_good; uint32_t flags; } faqcs_error_info;
+int  faqcs_first_error_device(faqcs_ctx *ctx, const faqcs_read_result *d_results, uint32_t n, faqcs_error_info *d_info);
+int  faqcs_first_error_host(const faqcs_read_result *results, uint32_t n, faqcs_error_info *info);
+
 /* Pipelined form of faqcs_submit(): returns a ticket; faqcs_wait(ticket) blocks until THAT batch's results have
  * landed in `results` (later batches may still be in flight: two input staging slots let the H2D copy of batch
  * k+1 overlap the kernels of batch k).  Host arenas / result arrays obtained from faqcs_host_alloc() are pinned,
@@ -574,6 +630,15 @@ void faqcs_host_free(void *p);
 /* Options::quality is mutable during a run: the NextSeq check bumps -q to 20 (FaQCs.cpp:272-277,404-414).
  * Takes effect for batches submitted afterwards. */
 int  faqcs_set_quality(faqcs_ctx *ctx, int quality);
+
+/* faqcs_params.input_quality_offset is what the reference detects on its first buffer (trim.cpp:599-617, the default: options.cpp:122),
+ * after Options exist.  Accepts what faqcs_create() accepts for that field (it checks nothing there) and rebuilds everything
+ * faqcs_create() derives from it: the parameter block of the kernels and the average-quality threshold table (--avg_q).  The call WAITS
+ * for the context's streams -- the table is device memory that enqueued kernels read --, so work enqueued before it sees the old offset
+ * and work enqueued after it the new one; it happens once per run.  A context may thus be created with a placeholder offset, used for
+ * faqcs_parse_device, the id check of faqcs_pair_device and faqcs_detect_device -- none of them reads the offset -- and set before its
+ * first submission.  (Submissions, faqcs_emit_device and the renderings of trimmed records read it.) */
+int  faqcs_set_input_quality_offset(faqcs_ctx *ctx, int input_quality_offset);
 
 /* Device address + length (uint64 units) of the additive counter block, so the host can run the one
  * collective this path needs -- all-reduce(sum, uint64) over RCCL -- in place before faqcs_finish(). */
