@@ -26,8 +26,10 @@
 //                               of the position x base registers (6-bit fields per class); a base outside the kept window is looked up
 //                               at (byte | 0x80), whose entry has the pre increment only.  The same increments, summed over the lane's
 //                               19 positions and then over the 8 lanes of the read (DPP), ARE the read's base counts before / inside
-//                               the window -- what a separate lane-per-read class pass (S-A, round 2) used to compute.  Two adjacent
-//                               upper-case N (the default -n 2) are found by a SWAR test on the same registers, only in reads with >= 2 N
+//                               the window -- what a separate lane-per-read class pass (S-A, round 2) used to compute.  With 8 lanes per
+//                               read the 8 steps of a chunk are added up as a reduce-scatter (totals_scatter).  Two adjacent upper-case N
+//                               (the default -n 2) are found by a SWAR test on the same registers, only in steps where a lane holds two N
+//                               or a lane's last and its neighbour's first position both hold one
 //   verdicts, one read per lane poly-N, average quality, low complexity (dinucleotide counts only for reads whose two commonest bases
 //                               both reach the threshold) -> the read's verdict
 //   epilogue, one read per lane result word, composition records, small histograms (equal cells of a chunk combined by one lane),
@@ -624,12 +626,65 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void trim_lds(
     // entry carries the pre increment only (input bytes >= 0x80 are no bases: a chunk that holds one is undone, patched and redone).
     // The lane's 19 increments are summed on the side (<= 19 per field), the 8 lanes of the read are added up by DPP (fields
     // widened to 12 bits after the first step: a read has up to 152 bases) and the lane whose turn it is (rl == t) keeps the
-    // totals: what S-A used to compute with a second lookup per base in the lane-per-read layout.
+    // totals: what S-A used to compute with a second lookup per base in the lane-per-read layout.  (So the 4- and 16-lane shapes; with 8 lanes
+    // per read and 8 steps per chunk the lanes add up only what they keep: totals_scatter below.)
     // MODE 0: count ; 1: take back the post increments of the reads flagged in i1 (vetoed after counting) ; 2: take back everything
     uint32_t tot_pe = 0, tot_po = 0, tot_ce = 0, tot_co = 0; // this lane's read: pre A | C << 12 | N << 24, pre T | G << 12, post ...
     uint32_t tot_pn = 0;                                      // (WIDE) pre N | post N << 16
     uint32_t seen7 = 0;                                       // OR of every counted base byte of the chunk (bit 7: abnormal input)
     bool pairhit = false;                                     // this lane's read: two adjacent upper-case N inside the kept window
+    // The read's totals as a REDUCE-SCATTER over the chunk's 8 steps (8 lanes per read, 8 reads per row): a lane adds up only what it will keep.
+    //   level 1, every step, 6-bit fields (<= 38): lanes 0-3 of a read take the sum of lanes {i, i + 4} at an even step, lanes 4-7 that of
+    //            {i - 4, i} at the odd step behind it -- row_shl:4 / row_shr:4 under a bank mask (a bank is four lanes): no select
+    //   level 2, once per four steps: lanes with bit 0 clear keep the first pair of steps (parked in rs_ap / rs_aq, still 6-bit fields),
+    //            the others the second; the partner's half comes by quad_perm xor 1 and is added with the even and the odd fields apart
+    //            (<= 76: 12 bits of room each).  The odd fields stay where they are, 6 bits up, until the end
+    //   level 3, once per chunk: lanes with bit 1 clear keep the first four steps (parked in tot_*), the others the last four (quad_perm xor 2)
+    // Lane i of a row ends up with the read of step  bit2(i) + 2 bit0(i) + 4 bit1(i);  totals_finish() puts every read into lane rl == t.
+    // (The usual first level -- xor 1 -- needs two selects per register and step pair; the bank mask can tell lanes 0-3 from 4-7 only.)
+    constexpr bool SCATTER = LPR == 8 && TPR == 8 && !WIDE;
+    uint32_t rs_p = 0, rs_q = 0, rs_ap = 0, rs_aq = 0;
+    const bool rs_k1 = (lane & 1) != 0, rs_k2 = (lane & 2) != 0;
+    auto totals_scatter = [&](const int t, const uint32_t tp, const uint32_t tq) {
+        if ((t & 1) == 0) {
+            rs_p = tp + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)tp, 0x104, 0xf, 0x5, false); // (lanes 4-7: replaced at the odd step)
+            rs_q = tq + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)tq, 0x104, 0xf, 0x5, false);
+            return;
+        }
+        const uint32_t up = tp + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)tp, 0x114, 0xf, 0xa, false);
+        const uint32_t uq = tq + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)tq, 0x114, 0xf, 0xa, false);
+        rs_p = (uint32_t)__builtin_amdgcn_update_dpp((int)rs_p, (int)up, 0xE4, 0xf, 0xa, false); // lanes 4-7 <- the odd step's sum
+        rs_q = (uint32_t)__builtin_amdgcn_update_dpp((int)rs_q, (int)uq, 0xE4, 0xf, 0xa, false);
+        if ((t & 2) == 0) { rs_ap = rs_p; rs_aq = rs_q; return; }
+        uint32_t v[4];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const uint32_t cur = i ? rs_q : rs_p, fst = i ? rs_aq : rs_ap;
+            const uint32_t keep = rs_k1 ? cur : fst, send = rs_k1 ? fst : cur;
+            const uint32_t got = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)send, 0xB1, 0xf, 0xf, false);
+            v[2 * i] = (keep & 0x3f03f03fu) + (got & 0x3f03f03fu);
+            v[2 * i + 1] = keep + got - v[2 * i]; // (the odd fields: as integers the two 6-bit words add up to the even plus the odd sums)
+        }
+        if ((t & 4) == 0) { tot_pe = v[0]; tot_po = v[1]; tot_ce = v[2]; tot_co = v[3]; return; }
+        uint32_t *const tot[4] = {&tot_pe, &tot_po, &tot_ce, &tot_co};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const uint32_t keep = rs_k2 ? v[i] : *tot[i], send = rs_k2 ? *tot[i] : v[i];
+            *tot[i] = keep + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)send, 0x4E, 0xf, 0xf, false);
+        }
+        tot_po >>= 6; tot_co >>= 6;
+    };
+    // behind a counting S loop that ran steps 0 .. t_done - 1 (fewer than 8: the launch's last chunk): the steps that are missing, with nothing
+    // to add, complete what is pending at every level; then the fixed permutation above is undone, once per chunk
+    auto totals_finish = [&](int t_done) {
+        if constexpr (SCATTER) {
+#pragma unroll 1
+            for (; t_done < TPR; ++t_done) totals_scatter(t_done, 0u, 0u);
+            const int src = rowb + (((rl & 1) << 2) | (rl >> 1)); // the lane that holds step rl
+            tot_pe = (uint32_t)__shfl((int)tot_pe, src); tot_po = (uint32_t)__shfl((int)tot_po, src);
+            tot_ce = (uint32_t)__shfl((int)tot_ce, src); tot_co = (uint32_t)__shfl((int)tot_co, src);
+        }
+    };
     auto base_step = [&](const int t, const uint32_t i0, const uint32_t i1, auto mode_t) {
         constexpr int MODE = decltype(mode_t)::value;
         const int len = (int)(i0 >> 16), a = (int)(i1 & AM), n = (int)((i1 >> AB) & AM);
@@ -662,25 +717,58 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void trim_lds(
         for (int k = 0; k < D; ++k) w[k] = __builtin_amdgcn_alignbyte(r[k + 1], r[k], sh) & t_bm[BMW * vb + k]; // a byte past the read: 0, no class
 #endif
         uint32_t tp = 0, tq = 0;
+        // The look-ups go out in batches of <= 7, and a batch's results are added -- to the position x base registers too -- while the
+        // next batch is in flight: two batches of results are live at a time.  (Left to the scheduler, the 2 C register adds sink to the
+        // bottom of the step and all C results stay live across the totals and the N test: the kernel's register peak.)
+        constexpr int SNB = (C + 6) / 7, SBL = (C + SNB - 1) / SNB; // batches, look-ups per batch
+        LdsPair2 e[C];
+        auto look = [&](const int b) {
 #pragma unroll
-        for (int j = 0; j < C; ++j) {
-            const int k = j >> 2;
-            if ((j & 3) == 0) {
-                if (MODE == 0) seen7 |= w[k];
-                w[k] ^= ~((EXT && chk) ? 0u : inw[k]) & 0x88888888u; // (w[k] is the table index from here on; the byte is put back for the N tests)
-            }
-            const uint32_t ad = ((j & 3) == 0 ? byte_x8<0>(w[k], three) : (j & 3) == 1 ? byte_x8<1>(w[k], three)
-                                 : (j & 3) == 2 ? byte_x8<2>(w[k], three) : byte_x8<3>(w[k], three)) + (uint32_t)(T::O_T3 * 4);
+            for (int j = b * SBL; j < (b + 1) * SBL && j < C; ++j) {
+                const int k = j >> 2;
+                if ((j & 3) == 0) {
+                    if (MODE == 0) seen7 |= w[k];
+                    w[k] ^= ~((EXT && chk) ? 0u : inw[k]) & 0x88888888u; // (w[k] is the table index from here on; the byte is put back for the N tests)
+                }
+                const uint32_t ad = ((j & 3) == 0 ? byte_x8<0>(w[k], three) : (j & 3) == 1 ? byte_x8<1>(w[k], three)
+                                     : (j & 3) == 2 ? byte_x8<2>(w[k], three) : byte_x8<3>(w[k], three)) + (uint32_t)(T::O_T3 * 4);
 #ifdef FAQCS_LDS_DIAG_UNIFORM_SLOOKUP // (diagnostic build, wrong results: every lane looks up the same entry)
-            const LdsPair2 e = *(lds_u2c_ptr)(size_t)((ad & 0u) + (uint32_t)(T::O_T3 * 4 + 8 * 'A'));
+                e[j] = *(lds_u2c_ptr)(size_t)((ad & 0u) + (uint32_t)(T::O_T3 * 4 + 8 * 'A'));
 #else
-            const LdsPair2 e = *(lds_u2c_ptr)(size_t)ad;
+                e[j] = *(lds_u2c_ptr)(size_t)ad;
 #endif
-            if (MODE == 0) { bpre[j] += e.x; bpost[j] += e.y; tp += e.x; tq += e.y; }
-            if (MODE == 1) bpost[j] -= e.y;
-            if (MODE == 2) { bpre[j] -= e.x; bpost[j] -= e.y; }
+            }
+        };
+        auto account = [&](const int b) {
+#pragma unroll
+            for (int j = b * SBL; j < (b + 1) * SBL && j < C; ++j) {
+                if (MODE == 0) { bpre[j] += e[j].x; bpost[j] += e[j].y; tp += e[j].x; tq += e[j].y; }
+                if (MODE == 1) bpost[j] -= e[j].y;
+                if (MODE == 2) { bpre[j] -= e[j].x; bpost[j] -= e[j].y; }
+                // (an add whose only use is the next step's is otherwise sunk into the loop's last block, behind the totals and the N test)
+                asm volatile("" : "+v"(bpre[j]), "+v"(bpost[j]));
+            }
+        };
+        look(0);
+#pragma unroll
+        for (int b = 1; b < SNB; ++b) {
+            __builtin_amdgcn_sched_barrier(0);
+            look(b);
+            __builtin_amdgcn_sched_barrier(0);
+            account(b - 1);
         }
+        __builtin_amdgcn_sched_barrier(0);
+        account(SNB - 1);
+        __builtin_amdgcn_sched_barrier(0);
         if (MODE == 0) {
+            const bool turn = rl == t;
+            // the lane's own N (any case) inside the kept window, for the gate of the adjacent-N test below: the top field of the UN-reduced tq
+            const uint32_t tq_lane = tq;
+            // (No diagnostic build prices the totals: what the kernel does behind the loop depends on their values -- with zeros every
+            // composition record meets in one bin of the fold, with made-up counts the verdicts veto every read.  DESIGN.md 4.1.)
+            if constexpr (SCATTER) {
+                totals_scatter(t, tp, tq);
+            } else {
             // the read's totals: 8 lanes, <= 19 per 6-bit field each; one step in 6-bit fields (<= 38), the rest in 12-bit fields
             tp += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)tp, 0xB1, 0xf, 0xf, false);
             tq += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)tq, 0xB1, 0xf, 0xf, false);
@@ -708,14 +796,22 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void trim_lds(
                 ce += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)ce, 0x140, 0xf, 0xf, false);
                 co += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)co, 0x140, 0xf, 0xf, false);
             }
-            const bool turn = rl == t;
             tot_pe = turn ? pe : tot_pe; tot_po = turn ? po : tot_po; tot_ce = turn ? ce : tot_ce; tot_co = turn ? co : tot_co;
             if (WIDE) tot_pn = turn ? pn : tot_pn;
-            // ---- upper-case N inside the kept window (count_poly_n, trim.cpp:578-597): looked at only when the read has enough N
-            // (any case) in its window to matter, or when it is judged without being counted (chk) ----
-            const uint32_t cN = WIDE ? pn >> 16 : ce >> 24;
+            }
+            // ---- upper-case N inside the kept window (count_poly_n, trim.cpp:578-597): looked at only where two adjacent N (any case)
+            // can be -- two N among this lane's C positions, or one at its last position and one at the first position of the next lane of
+            // the row (bit 24 of a post increment: the N field; the lane behind a row's last one belongs to another read or is none: at worst a
+            // step that enters for nothing) -- or when the read is judged without being counted (chk).  In one compare: the N field is the
+            // top field of tq_lane, and a seam pair adds one to a field that holds at least the one of the lane's last position ----
+            const uint32_t seam = e[C - 1].y & (uint32_t)__builtin_amdgcn_update_dpp(0, (int)e[0].y, 0x101, 0xf, 0xf, false) & 0x01000000u;
+#ifdef FAQCS_LDS_DIAG_S_NO_NBLOCK // (diagnostic build, wrong results: the adjacent-N test is never entered -- what the steps the gate lets through cost)
+            const bool n_gate = false;
+#else
+            const bool n_gate = tq_lane + seam >= 0x02000000u || chk;
+#endif
             // -n 2 (the default): two adjacent N, tested here; any other -n: judged after the loop, from the staged bases
-            if ((!EXT || P.max_poly_n == 2u) && __any(cN >= 2u || chk)) {
+            if ((!EXT || P.max_poly_n == 2u) && __any(n_gate)) {
                 uint32_t nb[D]; // bit 7 of a byte: upper-case 'N' inside the kept window
 #pragma unroll
                 for (int k = 0; k < D; ++k) {
@@ -736,10 +832,8 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void trim_lds(
                     // (C a multiple of 4: the neighbour of the lane's last position is not among its D dwords -- the next lane's first byte)
                     if (C % 4 == 0) hit |= (nb[D - 1] >> 24) & RW::next(nb[0] & 0x80u);
                     const bool rowhit = RW::all_or(hit) != 0u;
-                    pairhit = turn ? rowhit : pairhit;
+                    pairhit = turn ? rowhit : pairhit; // (a read whose step never enters keeps the `false` it has from in front of the loop)
                 }
-            } else if (MODE == 0) {
-                pairhit = turn ? false : pairhit;
             }
         }
     };
@@ -1250,29 +1344,38 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void trim_lds(
             FAQCS_STAMP(5)
 
             // ================= S: 8 lanes per read, the bases (base_step) ==============================================
-#define FAQCS_S_LOOP(I1, MODE)                                                                                        \
-    {                                                                                                                 \
-        _Pragma("unroll 1") for (int t = 0; t < TPR; ++t) {                                                          \
+#define FAQCS_S_BODY(I1, MODE)                                                                                        \
             if (base + (uint32_t)t >= n_reads) break; /* wave-uniform: no row has a read left */                      \
             const uint32_t a1_ = (uint32_t)__shfl((int)(I1), rowb + t);                                               \
             if (MODE == 1 && !__any(((a1_ >> FB) & 1u) != 0u)) continue;                                              \
             const uint32_t a0_ = (uint32_t)__shfl((int)si0, rowb + t);                                                \
-            base_step(t, a0_, a1_, std::integral_constant<int, MODE>{});                                              \
+            base_step(t, a0_, a1_, std::integral_constant<int, MODE>{});
+            // FLAT: the eight steps of the chunk's counting pass written out (the reduce-scatter of the totals does something else at every
+            // step: with t a constant no step carries a branch or a copy for it).  The rare passes stay loops.
+#define FAQCS_S_LOOP(I1, MODE, FLAT)                                                                                  \
+    {                                                                                                                 \
+        int t = 0;                                                                                                    \
+        if (MODE == 0) pairhit = false;                                                                               \
+        if constexpr (FLAT && SCATTER) {                                                                              \
+            _Pragma("unroll") for (; t < TPR; ++t) { FAQCS_S_BODY(I1, MODE) }                                         \
+        } else {                                                                                                      \
+            _Pragma("unroll 1") for (; t < TPR; ++t) { FAQCS_S_BODY(I1, MODE) }                                       \
         }                                                                                                             \
+        if (MODE == 0) totals_finish(t);                                                                              \
     }
             seen7 = 0;
-            FAQCS_S_LOOP(si1, 0)
+            FAQCS_S_LOOP(si1, 0, true)
             if (__any((seen7 & 0x80808080u) != 0u)) {
                 // a byte >= 0x80 among the bases: it was looked up as "outside the kept window".  Take the chunk back, blank such bytes
                 // in the slot (no class: what the reference's switch does with them, trim.cpp:831-857) and count again.
-                FAQCS_S_LOOP(si1, 2)
+                FAQCS_S_LOOP(si1, 2, false)
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll 1
                 for (int p = 0; __any(p < len); ++p) {
                     if (p < len && (lds_ld_u8(slot_b + rows + (uint32_t)p) & 0x80u)) lds_st_u8(slot_b + rows + (uint32_t)p, 0u);
                 }
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                FAQCS_S_LOOP(si1, 0)
+                FAQCS_S_LOOP(si1, 0, false)
             }
 
             FAQCS_STAMP(6)
@@ -1405,7 +1508,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void trim_lds(
             const bool veto = retc && !ret;
             if (__any(veto)) {
                 const uint32_t vi1 = (uint32_t)a | ((uint32_t)n << AB) | (veto ? 1u << FB : 0u) | (veto ? 1u << (FB + 1) : 0u);
-                FAQCS_S_LOOP(vi1, 1)
+                FAQCS_S_LOOP(vi1, 1, false)
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 stage(qual, cs, ce, shq, pad_len);
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1454,6 +1557,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void trim_lds(
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             }
 #undef FAQCS_S_LOOP
+#undef FAQCS_S_BODY
 
             // the slot is not read any more: request the next chunk's loads now, under the epilogue (p_off / p_end: its offsets,
             // fetched at the top of this chunk)
