@@ -685,16 +685,19 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void trim_lds(
             tot_ce = (uint32_t)__shfl((int)tot_ce, src); tot_co = (uint32_t)__shfl((int)tot_co, src);
         }
     };
-    auto base_step = [&](const int t, const uint32_t i0, const uint32_t i1, auto mode_t) {
-        constexpr int MODE = decltype(mode_t)::value;
+    uint32_t n_steps = 0; // (wave-uniform) bit t: step t of the counting pass tripped the gate of the adjacent-N test; looked at behind the loop
+    // What a lane works on in a step, from the step's two info words: w[] = its C staged bases (a byte past the read: 0), inw[] = 0xff for a
+    // byte inside the kept window.  base_step and the adjacent-N pass behind the loop (adjacent_n_pass) both start from here.
+    auto step_words = [&](const uint32_t i0, const uint32_t i1, uint32_t (&w)[D], uint32_t (&inw)[D]) {
         const int len = (int)(i0 >> 16), a = (int)(i1 & AM), n = (int)((i1 >> AB) & AM);
-        const bool post = ((i1 >> FB) & 1u) != 0u, counted = ((i1 >> (FB + 1)) & 1u) != 0u, chk = ((i1 >> (FB + 2)) & 1u) != 0u;
+        // (chk is set for a read that fails the average quality: without EXT there is no such test, and the bit is never set)
+        const bool post = ((i1 >> FB) & 1u) != 0u, counted = ((i1 >> (FB + 1)) & 1u) != 0u, chk = EXT && ((i1 >> (FB + 2)) & 1u) != 0u;
         const int vb = counted ? med3i(len - pbase, 0, C + 1) : 0; // (a read that is not counted: every byte reads as "past the read")
         // the kept window as the table lookups see it: empty for a read that is not kept (every base outside: pre increments only)
         const int lo = med3i(a - pbase, 0, C + 1), hi = (post || chk) ? med3i(a + n - pbase, 0, C + 1) : lo;
         const uint32_t qa = (slot_b + (i0 & 0xffffu) + (uint32_t)pbase) & ~3u;
         const uint32_t sh = ((i0 & 0xffffu) + (uint32_t)pbase + slot_b) & 3u;
-        uint32_t r[D + 1], w[D], inw[D];
+        uint32_t r[D + 1];
 #ifdef FAQCS_LDS_DIAG_LINEAR_LOADS
 #pragma unroll
         for (int k = 0; k <= D; ++k) r[k] = lds_ld(slot_b + (uint32_t)lane * 4u + 256u * (uint32_t)k);
@@ -716,6 +719,12 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void trim_lds(
 #else
         for (int k = 0; k < D; ++k) w[k] = __builtin_amdgcn_alignbyte(r[k + 1], r[k], sh) & t_bm[BMW * vb + k]; // a byte past the read: 0, no class
 #endif
+    };
+    auto base_step = [&](const int t, const uint32_t i0, const uint32_t i1, auto mode_t) {
+        constexpr int MODE = decltype(mode_t)::value;
+        const bool chk = EXT && ((i1 >> (FB + 2)) & 1u) != 0u;
+        uint32_t w[D], inw[D]; // (both dead behind the last look-up: the step holds no other use of them)
+        step_words(i0, i1, w, inw);
         uint32_t tp = 0, tq = 0;
         // The look-ups go out in batches of <= 7, and a batch's results are added -- to the position x base registers too -- while the
         // next batch is in flight: two batches of results are live at a time.  (Left to the scheduler, the 2 C register adds sink to the
@@ -728,7 +737,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void trim_lds(
                 const int k = j >> 2;
                 if ((j & 3) == 0) {
                     if (MODE == 0) seen7 |= w[k];
-                    w[k] ^= ~((EXT && chk) ? 0u : inw[k]) & 0x88888888u; // (w[k] is the table index from here on; the byte is put back for the N tests)
+                    w[k] ^= ~((EXT && chk) ? 0u : inw[k]) & 0x88888888u; // (w[k] is the table index from here on)
                 }
                 const uint32_t ad = ((j & 3) == 0 ? byte_x8<0>(w[k], three) : (j & 3) == 1 ? byte_x8<1>(w[k], three)
                                      : (j & 3) == 2 ? byte_x8<2>(w[k], three) : byte_x8<3>(w[k], three)) + (uint32_t)(T::O_T3 * 4);
@@ -761,7 +770,6 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void trim_lds(
         account(SNB - 1);
         __builtin_amdgcn_sched_barrier(0);
         if (MODE == 0) {
-            const bool turn = rl == t;
             // the lane's own N (any case) inside the kept window, for the gate of the adjacent-N test below: the top field of the UN-reduced tq
             const uint32_t tq_lane = tq;
             // (No diagnostic build prices the totals: what the kernel does behind the loop depends on their values -- with zeros every
@@ -770,6 +778,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void trim_lds(
                 totals_scatter(t, tp, tq);
             } else {
             // the read's totals: 8 lanes, <= 19 per 6-bit field each; one step in 6-bit fields (<= 38), the rest in 12-bit fields
+            const bool turn = rl == t;
             tp += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)tp, 0xB1, 0xf, 0xf, false);
             tq += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)tq, 0xB1, 0xf, 0xf, false);
             // (WIDE: a read can hold more than 255 N -- the two N counts get a register of their own, pre in the low and post in the high half)
@@ -805,36 +814,50 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void trim_lds(
             // step that enters for nothing) -- or when the read is judged without being counted (chk).  In one compare: the N field is the
             // top field of tq_lane, and a seam pair adds one to a field that holds at least the one of the lane's last position ----
             const uint32_t seam = e[C - 1].y & (uint32_t)__builtin_amdgcn_update_dpp(0, (int)e[0].y, 0x101, 0xf, 0xf, false) & 0x01000000u;
-#ifdef FAQCS_LDS_DIAG_S_NO_NBLOCK // (diagnostic build, wrong results: the adjacent-N test is never entered -- what the steps the gate lets through cost)
+#ifdef FAQCS_LDS_DIAG_S_NO_NBLOCK // (diagnostic build, wrong results: no step is ever flagged, the pass behind the loop never runs -- what gate, flags and pass cost)
             const bool n_gate = false;
 #else
-            const bool n_gate = tq_lane + seam >= 0x02000000u || chk;
+            // (`tq_lane + seam >= 0x02000000u || chk` in one compare: chk moved to where it counts as two N -- the top field holds <= C + 1,
+            // nothing is carried out of the word; without EXT the term is a constant 0)
+            const uint32_t judged = EXT ? (i1 << (23 - FB)) & 0x02000000u : 0u;
+            const bool n_gate = tq_lane + seam + judged >= 0x02000000u;
 #endif
-            // -n 2 (the default): two adjacent N, tested here; any other -n: judged after the loop, from the staged bases
-            if ((!EXT || P.max_poly_n == 2u) && __any(n_gate)) {
-                uint32_t nb[D]; // bit 7 of a byte: upper-case 'N' inside the kept window
+            // -n 2 (the default): two adjacent N; the step only records that it must be looked at, adjacent_n_pass (behind the loop) looks.
+            // Any other -n: judged after the loop, from the staged bases
+            if (!EXT || P.max_poly_n == 2u) n_steps |= __any(n_gate) ? 1u << t : 0u;
+        }
+    };
+    // The adjacent-N test of the steps that a counting pass flagged in n_steps, lowest step first, behind the pass: the step's words again
+    // (the staged bases are untouched until the verdicts), then the test itself.  Only reads of LDS.  About 4 % of the steps of ordinary
+    // data are flagged; inside the loop the test kept w[] and inw[] alive past the last look-up and put a branch into every step.
+    auto adjacent_n_pass = [&](const uint32_t s0, const uint32_t s1) {
+#pragma unroll 1
+        while (n_steps != 0u) {
+            const int t = uni(__builtin_ctz(n_steps));
+            n_steps &= n_steps - 1u;
+            const uint32_t a1_ = (uint32_t)__shfl((int)s1, rowb + t), a0_ = (uint32_t)__shfl((int)s0, rowb + t);
+            uint32_t w[D], inw[D];
+            step_words(a0_, a1_, w, inw);
+            uint32_t nb[D]; // bit 7 of a byte: upper-case 'N' inside the kept window
 #pragma unroll
-                for (int k = 0; k < D; ++k) {
-                    const uint32_t orig = w[k] ^ (~((EXT && chk) ? 0u : inw[k]) & 0x88888888u); // (the byte itself again)
-                    const uint32_t x = (orig & inw[k]) ^ 0x4e4e4e4eu;
-                    const uint32_t sx = (x & 0x7f7f7f7fu) + 0x7f7f7f7fu;
-                    nb[k] = ~(sx | x) & 0x80808080u;
-                }
-                { // two adjacent N: positions (j, j + 1), j one of the lane's C positions
-                    uint32_t hit = 0;
-#pragma unroll
-                    for (int k = 0; k < D; ++k) {
-                        uint32_t here = nb[k];
-                        if (4 * k + 4 > C) here &= low_bytes_(C - 4 * k); // j < C
-                        const uint32_t next = k + 1 < D ? __builtin_amdgcn_alignbyte(nb[k + 1], nb[k], 1u) : (nb[k] >> 8);
-                        hit |= here & next;
-                    }
-                    // (C a multiple of 4: the neighbour of the lane's last position is not among its D dwords -- the next lane's first byte)
-                    if (C % 4 == 0) hit |= (nb[D - 1] >> 24) & RW::next(nb[0] & 0x80u);
-                    const bool rowhit = RW::all_or(hit) != 0u;
-                    pairhit = turn ? rowhit : pairhit; // (a read whose step never enters keeps the `false` it has from in front of the loop)
-                }
+            for (int k = 0; k < D; ++k) {
+                const uint32_t x = (w[k] & inw[k]) ^ 0x4e4e4e4eu;
+                const uint32_t sx = (x & 0x7f7f7f7fu) + 0x7f7f7f7fu;
+                nb[k] = ~(sx | x) & 0x80808080u;
             }
+            // two adjacent N: positions (j, j + 1), j one of the lane's C positions
+            uint32_t hit = 0;
+#pragma unroll
+            for (int k = 0; k < D; ++k) {
+                uint32_t here = nb[k];
+                if (4 * k + 4 > C) here &= low_bytes_(C - 4 * k); // j < C
+                const uint32_t next = k + 1 < D ? __builtin_amdgcn_alignbyte(nb[k + 1], nb[k], 1u) : (nb[k] >> 8);
+                hit |= here & next;
+            }
+            // (C a multiple of 4: the neighbour of the lane's last position is not among its D dwords -- the next lane's first byte)
+            if (C % 4 == 0) hit |= (nb[D - 1] >> 24) & RW::next(nb[0] & 0x80u);
+            const bool rowhit = RW::all_or(hit) != 0u;
+            pairhit = rl == t ? rowhit : pairhit; // (a read whose step is never flagged keeps the `false` it has from in front of the loop)
         }
     };
     // (Measured and not kept: a 160-wide table grid with the four rows of a half wave started 0..3 positions apart, which makes
@@ -1351,17 +1374,18 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void trim_lds(
             const uint32_t a0_ = (uint32_t)__shfl((int)si0, rowb + t);                                                \
             base_step(t, a0_, a1_, std::integral_constant<int, MODE>{});
             // FLAT: the eight steps of the chunk's counting pass written out (the reduce-scatter of the totals does something else at every
-            // step: with t a constant no step carries a branch or a copy for it).  The rare passes stay loops.
+            // step: with t a constant no step carries a branch or a copy for it).  The rare passes stay loops.  Behind a counting pass, first
+            // one or recount alike: the adjacent-N test of the steps it flagged (the flags and the verdicts start from nothing in front of it).
 #define FAQCS_S_LOOP(I1, MODE, FLAT)                                                                                  \
     {                                                                                                                 \
         int t = 0;                                                                                                    \
-        if (MODE == 0) pairhit = false;                                                                               \
+        if (MODE == 0) { pairhit = false; n_steps = 0u; }                                                             \
         if constexpr (FLAT && SCATTER) {                                                                              \
             _Pragma("unroll") for (; t < TPR; ++t) { FAQCS_S_BODY(I1, MODE) }                                         \
         } else {                                                                                                      \
             _Pragma("unroll 1") for (; t < TPR; ++t) { FAQCS_S_BODY(I1, MODE) }                                       \
         }                                                                                                             \
-        if (MODE == 0) totals_finish(t);                                                                              \
+        if (MODE == 0) { totals_finish(t); adjacent_n_pass(si0, I1); }                                                \
     }
             seen7 = 0;
             FAQCS_S_LOOP(si1, 0, true)
