@@ -260,6 +260,8 @@ def load_library():
         "faqcs_render_pair_time_ms": (i32, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "faqcs_inflate_error_text": (C.c_char_p, [i32]),
         "faqcs_bgzf_index_host": (i32, [vp, u64, i32, vp, u32, C.POINTER(BgzfIndexInfo)]),
+        "faqcs_bgzf_index_device": (i32, [vp, vp, u64, i32, vp, u32, vp]),
+        "faqcs_bgzf_index_time_ms": (i32, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "faqcs_inflate_device": (i32, [vp, vp, u64, vp, u32, C.POINTER(InflateOut)]),
         "faqcs_inflate_host": (i32, [vp, u64, vp, u32, C.POINTER(InflateOut)]),
         "faqcs_inflate_time_ms": (i32, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),

@@ -1,5 +1,5 @@
 // faqcs_capi_seam.hip -- the device seams of the C ABI (include/faqcs_mi.h): faqcs_emit_device, faqcs_parse_device, faqcs_render_device,
-// faqcs_pair_device, faqcs_render_pair_device, faqcs_inflate_device and faqcs_deflate_device with their faqcs_*_time_ms, and the untimed
+// faqcs_pair_device, faqcs_render_pair_device, faqcs_bgzf_index_device, faqcs_inflate_device and faqcs_deflate_device with their faqcs_*_time_ms, and the untimed
 // faqcs_detect_device / faqcs_first_error_device.  Each of the timed ones is two stages of kernels between the marks of a
 // PackStage; the host statements of the same rules, and the argument checks shared with them, are in faqcs_host.cpp.
 #include "faqcs_ctx.h"
@@ -127,6 +127,20 @@ extern "C" int faqcs_render_pair_device(faqcs_ctx *c, int file, const faqcs_mate
 }
 
 extern "C" int faqcs_render_pair_time_ms(faqcs_ctx *c, double *scan_ms, double *gather_ms) { return stage_times(c, &faqcs_ctx::render_pair, "faqcs_render_pair_time_ms: no paired rendering on this context yet", scan_ms, gather_ms); }
+
+extern "C" int faqcs_bgzf_index_device(faqcs_ctx *c, const uint8_t *d_comp, uint64_t n_comp, int final, uint32_t *d_member_offset, uint32_t capacity_members,
+                                       faqcs_bgzf_index_info *d_info)
+{
+    if (!c) return fail(FAQCS_E_INVAL, "null ctx");
+    if (int rc = bgzf_index_check_args("faqcs_bgzf_index_device", d_comp, n_comp, d_member_offset, d_info)) return rc;
+    if (int rc = c->bgzf_index.begin(c, faqcs_bgzf_index_scratch_bytes(n_comp))) return rc;
+    HIPCHK(faqcs_launch_bgzf_index_candidates(d_comp, n_comp, c->bgzf_index.scratch.p, c->n_cu, c->compute));
+    if (int rc = c->bgzf_index.mark(1)) return rc;
+    HIPCHK(faqcs_launch_bgzf_index_chain(d_comp, n_comp, final ? 1 : 0, d_member_offset, capacity_members, d_info, c->bgzf_index.scratch.p, c->n_cu, c->compute));
+    return c->bgzf_index.mark(2);
+}
+
+extern "C" int faqcs_bgzf_index_time_ms(faqcs_ctx *c, double *candidates_ms, double *chain_ms) { return stage_times(c, &faqcs_ctx::bgzf_index, "faqcs_bgzf_index_time_ms: no index on this context yet", candidates_ms, chain_ms); }
 
 extern "C" int faqcs_inflate_device(faqcs_ctx *c, const uint8_t *d_comp, uint64_t n_comp, const uint32_t *d_member_offset, uint32_t n_members, const faqcs_inflate_out *out)
 {

@@ -80,6 +80,10 @@ hipError_t faqcs_launch_render_pair_gather(bool trimmed, const MateDev &m1, cons
 size_t faqcs_inflate_scratch_bytes(uint32_t n_members);
 hipError_t faqcs_launch_inflate_scan(const uint8_t *comp, unsigned long long n_comp, const uint32_t *moff, uint32_t n, const faqcs_inflate_out *out, void *scratch, hipStream_t st);
 hipError_t faqcs_launch_inflate_decode(const uint8_t *comp, const uint32_t *moff, uint32_t n, const faqcs_inflate_out *out, void *scratch, int n_cu, hipStream_t st);
+size_t faqcs_bgzf_index_scratch_bytes(unsigned long long n_comp);
+hipError_t faqcs_launch_bgzf_index_candidates(const uint8_t *comp, unsigned long long n_comp, void *scratch, int n_cu, hipStream_t st);
+hipError_t faqcs_launch_bgzf_index_chain(const uint8_t *comp, unsigned long long n_comp, int final, uint32_t *member_offset, uint32_t capacity, faqcs_bgzf_index_info *info,
+                                         void *scratch, int n_cu, hipStream_t st);
 size_t faqcs_deflate_scratch_bytes(uint32_t n, uint32_t n_data, uint32_t member_bytes, int n_cu);
 hipError_t faqcs_launch_deflate_encode(const uint8_t *text, unsigned long long n_text, uint32_t member_bytes, uint32_t n, uint32_t n_data, int mode, void *scratch, int n_cu, hipStream_t st);
 hipError_t faqcs_launch_deflate_gather(uint32_t member_bytes, uint32_t n, uint32_t n_data, const faqcs_deflate_out *out, void *scratch, int n_cu, hipStream_t st);
@@ -177,6 +181,7 @@ struct faqcs_ctx {
     PackStage pair;   // the partial of every tile of pairs (first mismatch, sums) | ids + route + partials, finishing block
     PackStage render_pair; // as render, over the 2 n_pairs candidates of the two mates | scan, gather
     PackStage inflate; // the header fields, the position and the status of every member, the scan's tile sums | scan, decode
+    PackStage bgzf_index; // the candidates' positions, sizes, jump tables and ranks, the tiles' counts | candidates, chain
     PackStage deflate; // every member's slot, size and position, a block's tokens, the scan's tile sums | encode, gather
     PackStage detect;  // faqcs_detect_device and faqcs_first_error_device: the partial (first hit) of every tile | only the scratch is used: the stage is not timed
     // per-read composition records (trim kernel -> composition_histogram).  Two sets: the histogram kernels of

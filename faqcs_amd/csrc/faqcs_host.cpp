@@ -185,10 +185,17 @@ static const char *const INFLATE_TEXT[] = {"", "bgzf: not a BGZF member header",
                                            "bgzf: invalid deflate data", "bgzf: the CRC-32 differs from the trailer", "bgzf: the last member is incomplete"};
 extern "C" const char *faqcs_inflate_error_text(int code) { return code >= 0 && code <= FAQCS_INFLATE_E_TRUNCATED ? INFLATE_TEXT[code] : nullptr; }
 
+int bgzf_index_check_args(const char *who, const uint8_t *comp, uint64_t n_comp, const uint32_t *member_offset, const faqcs_bgzf_index_info *info)
+{
+    const std::string w(who);
+    if (!info || !member_offset || (!comp && n_comp)) return fail(FAQCS_E_INVAL, w + ": null input, offsets or info");
+    if (n_comp >= (1ull << 32)) return fail(FAQCS_E_INVAL, w + ": 2^32 bytes or more must be cut into chunks (final = 0, consumed)");
+    return 0;
+}
+
 extern "C" int faqcs_bgzf_index_host(const uint8_t *comp, uint64_t n_comp, int final, uint32_t *member_offset, uint32_t capacity_members, faqcs_bgzf_index_info *info)
 {
-    if (!info || !member_offset || (!comp && n_comp)) return fail(FAQCS_E_INVAL, "faqcs_bgzf_index_host: null input, offsets or info");
-    if (n_comp >= (1ull << 32)) return fail(FAQCS_E_INVAL, "faqcs_bgzf_index_host: 2^32 bytes or more must be cut into chunks (final = 0, consumed)");
+    if (int rc = bgzf_index_check_args("faqcs_bgzf_index_host", comp, n_comp, member_offset, info)) return rc;
     faqcs_inflate::IndexInfo ii{};
     faqcs_inflate::bgzf_index(comp, n_comp, final, member_offset, capacity_members, ii);
     info->consumed = ii.consumed; info->n_members = ii.n_members; info->overflow = ii.overflow; info->error = ii.error; info->reserved = 0;

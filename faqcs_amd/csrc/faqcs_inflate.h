@@ -1,5 +1,6 @@
 // faqcs_inflate.h -- the decoder core of faqcs_inflate_device / faqcs_inflate_host (include/faqcs_mi.h): BGZF member header, canonical
-// Huffman tables with zlib's acceptance rules, symbol decode, length / distance arithmetic, the block loop and the CRC-32 arithmetic.
+// Huffman tables with zlib's acceptance rules, symbol decode, length / distance arithmetic, the block loop and the CRC-32 arithmetic; at
+// the end, the BSIZE walk of faqcs_bgzf_index_host and the per-position decision it shares with faqcs_bgzf_index_device's kernels.
 // The SAME text compiles for the host (faqcs_host.cpp: faqcs_inflate_host; tools/inflate_host_fuzz.cpp under the sanitizers) and for
 // gfx950 (faqcs_inflate_kernel.hip), the way faqcs_skm.h does: every bound the decoder checks -- input that runs out, a distance in
 // front of the member, output beyond ISIZE -- is checked HERE, before a Sink is asked to move a byte, so what the CPU tests and the
@@ -408,32 +409,52 @@ inline int inflate_member_host(const uint8_t *p, uint64_t size, Tables &T, uint8
 
 struct IndexInfo { uint64_t consumed; uint32_t n_members, overflow; int32_t error; };
 
+// What the walk of the BSIZE chain decides at position p of comp[0 .. n) (p <= n), from the bytes comp[p .. n) alone.  The host walk
+// (bgzf_index) and the kernels of faqcs_bgzf_index_device (faqcs_bgzf_index_kernel.hip) compile this text: a position is a member's for
+// both or for neither.
+//   AT_MEMBER    a whole member of ms bytes (MIN_MEMBER <= ms <= n - p): the walk goes on at p + ms
+//   AT_STOP      p == n: the data ends behind a member, consumed = p
+//   AT_END       not gzip: the data ends here, consumed = n
+//   AT_HEADER    a gzip member that is not BGZF, no BC subfield, or a stated size below MIN_MEMBER: E_HEADER, consumed = p
+//   AT_PARTIAL   what is there of a header or a member is sound, but not all of it is there: E_TRUNCATED when final, consumed = p
+enum { AT_MEMBER = 0, AT_STOP, AT_END, AT_HEADER, AT_PARTIAL };
+INF_HD int bgzf_index_at(const uint8_t *comp, uint64_t n, uint64_t p, uint32_t &ms)
+{
+    ms = 0;
+    const uint64_t avail = n - p;
+    if (!avail) return AT_STOP;
+    if (comp[p] != 31 || (avail >= 2 && comp[p + 1] != 139)) return AT_END;
+    if (avail >= 4 && (comp[p + 2] != 8 || !(comp[p + 3] & 4))) return AT_HEADER;
+    bool whole = avail >= 18 && avail >= 12ull + le16(comp + p + 10);
+    if (whole) {
+        ms = bgzf_member_size(comp + p, avail);
+        if (ms < MIN_MEMBER) return AT_HEADER; // no BC subfield
+        whole = ms <= avail;
+    }
+    return whole ? AT_MEMBER : AT_PARTIAL;
+}
+// consumed and error of a walk that stops at position p with the decision `at` (not AT_MEMBER)
+INF_HD void bgzf_index_stop(int at, uint64_t n, uint64_t p, int final, uint64_t &consumed, int32_t &error)
+{
+    consumed = at == AT_END ? n : p;
+    error = at == AT_HEADER ? ST_E_HEADER : (at == AT_PARTIAL && final) ? ST_E_TRUNCATED : ST_OK;
+}
+
 // The BSIZE chain of comp[0 .. n) from byte 0: member k is comp[member_offset[k] .. member_offset[k + 1]).  See faqcs_bgzf_index_host.
 inline void bgzf_index(const uint8_t *comp, uint64_t n, int final, uint32_t *member_offset, uint32_t capacity, IndexInfo &info)
 {
     for (int pass = 0; pass < 2; ++pass) {
         uint64_t p = 0;
-        uint32_t k = 0;
-        int err = ST_OK;
+        uint32_t k = 0, ms;
+        int at;
         if (pass) member_offset[0] = 0;
-        for (;;) {
-            const uint64_t avail = n - p;
-            if (!avail) break;
-            if (comp[p] != 31 || (avail >= 2 && comp[p + 1] != 139)) { p = n; break; } // not gzip: the data ends here
-            if (avail >= 4 && (comp[p + 2] != 8 || !(comp[p + 3] & 4))) { err = ST_E_HEADER; break; } // a gzip member that is not BGZF
-            bool whole = avail >= 18 && avail >= 12ull + le16(comp + p + 10);
-            uint32_t ms = 0;
-            if (whole) {
-                ms = bgzf_member_size(comp + p, avail);
-                if (ms < MIN_MEMBER) { err = ST_E_HEADER; break; } // no BC subfield
-                whole = ms <= avail;
-            }
-            if (!whole) { if (final) err = ST_E_TRUNCATED; break; }
+        while ((at = bgzf_index_at(comp, n, p, ms)) == AT_MEMBER) {
             if (pass) member_offset[k + 1] = (uint32_t)(p + ms);
             p += ms; ++k;
         }
         if (pass) break;
-        info.consumed = p; info.n_members = k; info.error = err;
+        bgzf_index_stop(at, n, p, final, info.consumed, info.error);
+        info.n_members = k;
         info.overflow = k > capacity ? 1u : 0u;
         if (info.overflow) break;
     }

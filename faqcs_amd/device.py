@@ -1,5 +1,5 @@
 """Torch-facing helpers of the device seam: inputs and outputs are torch tensors that live on the GPU; the work is the
-library's HIP kernels (faqcs_emit_device, faqcs_render_device, faqcs_pair_device, faqcs_render_pair_device, faqcs_inflate_device,
+library's HIP kernels (faqcs_emit_device, faqcs_render_device, faqcs_pair_device, faqcs_render_pair_device, faqcs_bgzf_index_device, faqcs_inflate_device,
 faqcs_deflate_device, faqcs_detect_device), never torch ops."""
 import ctypes as C
 
@@ -189,12 +189,42 @@ def paired_files(engine, mate1, mate2, route, n_pairs, files=(capi.FILE_QC1, cap
     return res
 
 
-def inflated_text(engine, comp, member_offset=None, capacity=None):
+def bgzf_index(engine, comp, final=True, capacity=None):
+    """Where the BGZF members of `comp` are, found on the device (faqcs_bgzf_index_device): `comp` never leaves the card.
+
+    comp: uint8 CUDA tensor, the compressed bytes (any alignment); final: an incomplete last member is an error (True) or left to the
+    caller (False); capacity: members to make room for (default: one per 16 KiB and 64 more, and the call is repeated once with what
+    info asks for when that is too little).  Returns (member_offset, n_members, consumed, error): int32 CUDA tensor [n_members + 1] (bit
+    pattern of uint32) -- member k is comp[member_offset[k] : member_offset[k + 1]] --, where the next chunk starts, and a capi.INFLATE_*
+    code, the error of member n_members: field for field what engine.bgzf_index_host() returns for the same bytes."""
+    import torch
+
+    dev = comp.device
+    comp = comp.contiguous()
+    n_comp = int(comp.numel())
+    cap = n_comp // 16384 + 64 if capacity is None else int(capacity)
+    info = torch.zeros(3, dtype=torch.int64, device=dev)
+    torch.cuda.current_stream(dev).synchronize()  # the library's compute stream is its own: the input must be complete
+    for attempt in range(2):
+        moff = torch.empty(cap + 1, dtype=torch.int32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        engine.bgzf_index_device(comp.data_ptr() if n_comp else None, n_comp, final, moff.data_ptr(), cap, info.data_ptr())
+        engine.sync()
+        p = capi.BgzfIndexInfo.from_buffer_copy(info.cpu().numpy().tobytes())
+        if not p.overflow:
+            return moff[:p.n_members + 1], int(p.n_members), int(p.consumed), int(p.error)
+        if attempt:
+            raise FaqcsError(capi.E_INVAL, "faqcs_bgzf_index_device: %d members, the offsets hold %d" % (p.n_members, cap))
+        cap = int(p.n_members)
+
+
+def inflated_text(engine, comp, member_offset=None, capacity=None, index="host"):
     """The text of BGZF-compressed input, inflated on the device (faqcs_inflate_device).
 
     comp: uint8 CUDA tensor, the compressed bytes (whole members; any alignment); member_offset: int32 / uint32 tensor or numpy array
-    [n_members + 1], or None: the members are found on the host (faqcs_bgzf_index_host), which copies `comp` there -- a caller that
-    uploads a file has those bytes on the host already and passes the offsets.  capacity: bytes of text to make room for (default
+    [n_members + 1], or None: the members are found on the host (index="host": faqcs_bgzf_index_host, which copies `comp` there -- a
+    caller that uploads a file has those bytes on the host already and passes the offsets) or on the device (index="device":
+    faqcs_bgzf_index_device, `comp` never leaves the card).  capacity: bytes of text to make room for (default
     65 536 per member, which no member exceeds).  Returns (text, member_text_offset): uint8 [n_bytes] -- a view that starts 16-byte
     aligned, 64 bytes into its storage, with 64 spare bytes behind: a valid d_text for faqcs_parse_device() --, int32 [n_members + 1]
     (bit pattern of uint32).  A bad member raises FaqcsError with faqcs_inflate_error_text and the member's index."""
@@ -202,6 +232,12 @@ def inflated_text(engine, comp, member_offset=None, capacity=None):
     import torch
 
     dev = comp.device
+    if index not in ("host", "device"):
+        raise ValueError("index: 'host' or 'device'")
+    if member_offset is None and index == "device":
+        member_offset, n_mem, consumed, err = bgzf_index(engine, comp, True)
+        if err:
+            raise FaqcsError(capi.E_INVAL, "member %d: %s" % (n_mem, engine.lib.faqcs_inflate_error_text(err).decode()))
     if member_offset is None:
         from .engine import bgzf_index_host
         moff, consumed, err = bgzf_index_host(comp.cpu().numpy(), True, engine.lib)

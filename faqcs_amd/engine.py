@@ -207,6 +207,18 @@ class HipEngine:
         _check(self.lib, self.lib.faqcs_deflate_time_ms(self.ctx, C.byref(a), C.byref(g)))
         return a.value, g.value
 
+    def bgzf_index_device(self, d_comp, n_comp, final, d_member_offset, capacity_members, d_info):
+        """faqcs_bgzf_index_device: where the BGZF members of compressed bytes in device memory are (d_comp: device address, any alignment)
+        -> d_member_offset (device uint32 [capacity_members + 1]) and d_info (a faqcs_bgzf_index_info in device memory), field for field
+        what bgzf_index_host() finds.  Enqueued; sync() waits."""
+        _check(self.lib, self.lib.faqcs_bgzf_index_device(self.ctx, d_comp, int(n_comp), 1 if final else 0, d_member_offset, int(capacity_members), d_info))
+
+    def bgzf_index_time_ms(self):
+        """(candidates ms, chain ms) of the last bgzf_index_device() on this engine (HIP events on the compute stream); waits for it."""
+        a, g = C.c_double(), C.c_double()
+        _check(self.lib, self.lib.faqcs_bgzf_index_time_ms(self.ctx, C.byref(a), C.byref(g)))
+        return a.value, g.value
+
     def bgzf_index_host(self, comp, final=True):
         """bgzf_index_host() of this module on the engine's library."""
         return bgzf_index_host(comp, final, self.lib)

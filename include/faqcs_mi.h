@@ -34,7 +34,7 @@ extern "C" {
  * Round 6 adds faqcs_kmer_finish_pass, and faqcs_sync() no longer counts the k-mers that wait in the open group (see below).
  * faqcs_emit_device (the trimmed, edited reads packed on the device) is a new entry point with structures of its own, and so are
  * faqcs_parse_device / faqcs_parse_host (FASTQ text to a packed batch) and faqcs_render_device / faqcs_render_host (the FASTQ text of the
- * output files), and faqcs_inflate_device / faqcs_inflate_host / faqcs_bgzf_index_host (BGZF members to that text),
+ * output files), and faqcs_inflate_device / faqcs_inflate_host / faqcs_bgzf_index_host / faqcs_bgzf_index_device (BGZF members to that text),
  * and faqcs_deflate_device / faqcs_deflate_host (text to BGZF members), and faqcs_pair_device / faqcs_pair_host /
  * faqcs_render_pair_device / faqcs_render_pair_host (the two mates of a paired run from two batches), and faqcs_detect_device /
  * faqcs_detect_host / faqcs_first_error_device / faqcs_first_error_host / faqcs_set_input_quality_offset (the decisions around trim()). */
@@ -442,8 +442,29 @@ int  faqcs_render_pair_host(const faqcs_params *p, int file, const faqcs_mate *m
  *   Bytes behind the last member that do not start a gzip header (1f 8b) end the data without an error, as they do for zlib's gzread
  *   (DESIGN.md section 8): consumed = n_comp.  A gzip header that is not a BGZF member's is FAQCS_INFLATE_E_HEADER of member n_members, and
  *   consumed is where it starts.  n_members > capacity_members: overflow = 1, info is complete and nothing else is written.
- *   n_comp >= 2^32 or a null pointer is FAQCS_E_INVAL.  There is no device-side index: the chain is a serial pointer chase -- each header
- *   says where the next one is -- that the host does in microseconds on bytes it has just read and is about to upload.
+ *   n_comp >= 2^32 or a null pointer is FAQCS_E_INVAL.  This is the right form for bytes the host has just read and is about to upload:
+ *   the chain is a serial pointer chase -- each header says where the next one is -- that the host does in microseconds.
+ * faqcs_bgzf_index_device: the same call for compressed bytes that are in device memory already (a peer's buffer, a tensor, an RDMA
+ *   landing buffer) and would have to come back to the host only to be walked.  Every pointer but ctx is a DEVICE pointer, d_info
+ *   included.  Enqueued on the context's compute stream, returns at once; faqcs_sync() waits.  No alignment is asked of d_comp and nothing
+ *   outside d_comp[0 .. n_comp) is read.  The contract is faqcs_bgzf_index_host's, field for field:
+ *   final         0: an incomplete last member is left to the caller and consumed says where the next chunk starts; 1: it is
+ *                 FAQCS_INFLATE_E_TRUNCATED of member n_members
+ *   end of data   bytes that do not start 1f 8b end the data without an error, consumed = n_comp; a gzip header that is not a BGZF
+ *                 member's is FAQCS_INFLATE_E_HEADER with consumed at its start
+ *   short input   the host walk looks at what there is: one byte 1f alone, 1f 8b with fewer than 4 bytes, a sound start with fewer than
+ *                 18 bytes or fewer than 12 + XLEN are an incomplete member (see final); a byte that is wrong is judged as soon as it is there
+ *   BC subfield   subfields in front of BC are skipped, a BC with SLEN != 2 is passed over, a BC whose six bytes overrun XLEN is not
+ *                 taken; no BC, or a stated size below 26, is FAQCS_INFLATE_E_HEADER
+ *   members       only what the chain from byte 0 lands on is a member: bytes inside a member that look like a header (in a stored block,
+ *                 FNAME, FCOMMENT, an FEXTRA subfield) are not, whatever they state
+ *   overflow      n_members > capacity_members: overflow = 1, info is complete and nothing else is written
+ *   error         d_member_offset[0 .. n_members] of the members in front of the error are written, as the host writes them
+ *   FAQCS_E_INVAL: n_comp >= 2^32, a null ctx, d_member_offset or d_info, a null d_comp with n_comp > 0.
+ *   Scratch is the library's, grown on demand and freed by faqcs_destroy(): 6 bytes per compressed byte (18 bytes for each of the
+ *   n_comp / 3 positions that can look like a member's header at the same time), so chunks of 256 MiB or less are the sensible unit.
+ *   faqcs_bgzf_index_time_ms: the two stages of the context's last call (candidates: every position tested, the candidates in order;
+ *   chain: the chain from byte 0 over them, info, the offsets).
  * faqcs_inflate_device: every pointer but ctx and out is a DEVICE pointer, out->info included.  Enqueued on the context's compute stream,
  * returns at once; faqcs_sync() waits.  No alignment is asked of d_comp; member k is d_comp[d_member_offset[k] .. d_member_offset[k + 1]).
  *   before decoding   every member's header and trailer are checked and the ISIZE of the members give each its position in the text and the
@@ -481,6 +502,9 @@ typedef struct faqcs_bgzf_index_info {
 } faqcs_bgzf_index_info;
 int  faqcs_bgzf_index_host(const uint8_t *comp, uint64_t n_comp, int final, uint32_t *member_offset, uint32_t capacity_members,
                            faqcs_bgzf_index_info *info);
+int  faqcs_bgzf_index_device(faqcs_ctx *ctx, const uint8_t *d_comp, uint64_t n_comp, int final, uint32_t *d_member_offset,
+                             uint32_t capacity_members, faqcs_bgzf_index_info *d_info);
+int  faqcs_bgzf_index_time_ms(faqcs_ctx *ctx, double *candidates_ms, double *chain_ms);
 
 typedef struct faqcs_inflate_info {
     uint64_t n_bytes;      /* text bytes of the members in front of the first bad one (all of them when error == 0) */
