@@ -108,6 +108,7 @@ PAIR_FILES = ("QC.1.trimmed.fastq", "QC.2.trimmed.fastq", "QC.unpaired.trimmed.f
 
 # FAQCS_INFLATE_*: faqcs_inflate_info.error / faqcs_bgzf_index_info.error, the error of member n_members
 INFLATE_OK, INFLATE_E_HEADER, INFLATE_E_LENGTH, INFLATE_E_DATA, INFLATE_E_CRC, INFLATE_E_TRUNCATED = range(6)
+INFLATE_E_SERIAL = 16  # faqcs_gunzip_info.error only: the stream does not split into pieces
 
 
 class BgzfIndexInfo(C.Structure):
@@ -123,6 +124,20 @@ class InflateInfo(C.Structure):
 class InflateOut(C.Structure):
     """faqcs_inflate_out: the caller's output arrays (device pointers for faqcs_inflate_device, host pointers for faqcs_inflate_host)."""
     _fields_ = [("text", C.c_void_p), ("capacity_bytes", C.c_uint64), ("member_text_offset", C.c_void_p), ("info", C.c_void_p)]
+
+
+class GunzipInfo(C.Structure):
+    """faqcs_gunzip_info: what the text of the members needs, the bytes they cover, the first bad member, and what the speculation did."""
+    _fields_ = [("n_bytes", C.c_uint64), ("consumed", C.c_uint64), ("n_members", C.c_uint32), ("overflow", C.c_uint32), ("error", C.c_int32),
+                ("n_pieces", C.c_uint32), ("n_fixups", C.c_uint32), ("n_rounds", C.c_uint32)]
+
+
+class GunzipOut(C.Structure):
+    """faqcs_gunzip_out: the caller's output (device pointers for faqcs_gunzip_device, host pointers for faqcs_gunzip_host)."""
+    _fields_ = [("text", C.c_void_p), ("capacity_bytes", C.c_uint64), ("info", C.c_void_p)]
+
+
+GUNZIP_DEFAULT_PIECE, GUNZIP_DEFAULT_ROUNDS = 64 << 10, 32  # what piece_bytes = 0 and max_rounds = 0 mean
 
 
 class DeflateInfo(C.Structure):
@@ -265,6 +280,9 @@ def load_library():
         "faqcs_inflate_device": (i32, [vp, vp, u64, vp, u32, C.POINTER(InflateOut)]),
         "faqcs_inflate_host": (i32, [vp, u64, vp, u32, C.POINTER(InflateOut)]),
         "faqcs_inflate_time_ms": (i32, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+        "faqcs_gunzip_device": (i32, [vp, vp, u64, u32, u32, C.POINTER(GunzipOut)]),
+        "faqcs_gunzip_host": (i32, [vp, u64, u32, u32, C.POINTER(GunzipOut)]),
+        "faqcs_gunzip_time_ms": (i32, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "faqcs_deflate_device": (i32, [vp, vp, u64, u32, i32, C.POINTER(DeflateOut)]),
         "faqcs_deflate_host": (i32, [vp, u64, u32, i32, C.POINTER(DeflateOut)]),
         "faqcs_deflate_device_mode": (i32, [vp, vp, u64, u32, i32, i32, C.POINTER(DeflateOut)]),

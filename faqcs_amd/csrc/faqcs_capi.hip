@@ -238,7 +238,7 @@ extern "C" void faqcs_destroy(faqcs_ctx *c)
     for (auto &t : c->timings) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); (void)hipEventDestroy(t.p); (void)hipEventDestroy(t.k0); (void)hipEventDestroy(t.k1); }
     if (c->comm) comm_release(c->comm);
     if (c->comm_ev) (void)hipEventDestroy(c->comm_ev);
-    c->emit.release(); c->parse.release(); c->render.release(); c->pair.release(); c->render_pair.release(); c->inflate.release(); c->bgzf_index.release(); c->deflate.release(); c->detect.release();
+    c->emit.release(); c->parse.release(); c->render.release(); c->pair.release(); c->render_pair.release(); c->inflate.release(); c->bgzf_index.release(); c->deflate.release(); c->detect.release(); c->gunzip.release();
     if (c->ins_a) (void)hipEventDestroy(c->ins_a);
     if (c->ins_b) (void)hipEventDestroy(c->ins_b);
     for (int k = 0; k < 2; ++k) { if (c->fwd_free[k]) (void)hipEventDestroy(c->fwd_free[k]); if (c->fwd_copied[k]) (void)hipEventDestroy(c->fwd_copied[k]); c->fwd_items[k].release(); }

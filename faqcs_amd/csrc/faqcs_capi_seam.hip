@@ -2,8 +2,10 @@
 // faqcs_pair_device, faqcs_render_pair_device, faqcs_bgzf_index_device, faqcs_inflate_device and faqcs_deflate_device with their faqcs_*_time_ms, and the untimed
 // faqcs_detect_device / faqcs_first_error_device.  Each of the timed ones is two stages of kernels between the marks of a
 // PackStage; the host statements of the same rules, and the argument checks shared with them, are in faqcs_host.cpp.
+// faqcs_gunzip_device is the one call that blocks: the walk of faqcs_gunzip.h runs here, on the host, between its passes.
 #include "faqcs_ctx.h"
 #include "faqcs_deflate.h"
+#include "faqcs_gunzip.h"
 
 int PackStage::begin(faqcs_ctx *c, size_t scratch_bytes)
 {
@@ -154,6 +156,112 @@ extern "C" int faqcs_inflate_device(faqcs_ctx *c, const uint8_t *d_comp, uint64_
 }
 
 extern "C" int faqcs_inflate_time_ms(faqcs_ctx *c, double *scan_ms, double *decode_ms) { return stage_times(c, &faqcs_ctx::inflate, "faqcs_inflate_time_ms: no inflate on this context yet", scan_ms, decode_ms); }
+
+// faqcs_gunzip_device's Backend of gunzip_run (faqcs_gunzip.h): the compressed bytes and the passes are on the device, the walk's few bytes
+// per piece come back to the host.  Every step is followed by a wait, so the call blocks; a pass is timed between two events.
+namespace {
+struct GunzipDevice {
+    faqcs_ctx *c;
+    const uint8_t *comp;
+    uint32_t n_comp, piece_bytes;
+    uint8_t *text;
+    int down(void *dst, const void *src, size_t n)
+    {
+        HIPCHK(hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, c->compute));
+        HIPCHK(hipStreamSynchronize(c->compute));
+        return 0;
+    }
+    int begin() { HIPCHK(hipEventRecord(c->gunzip.ev[0], c->compute)); return 0; }
+    int end(int stage)
+    {
+        float ms = 0.f;
+        HIPCHK(hipEventRecord(c->gunzip.ev[1], c->compute));
+        HIPCHK(hipEventSynchronize(c->gunzip.ev[1]));
+        HIPCHK(hipEventElapsedTime(&ms, c->gunzip.ev[0], c->gunzip.ev[1]));
+        c->gunzip.ms[stage] += ms;
+        return 0;
+    }
+    int fetch(uint64_t p, uint32_t n, uint8_t *dst) { return down(dst, comp + p, n); }
+    int count_grid(faqcs_gunzip::Piece *grid, uint32_t n_grid)
+    {
+        HIPCHK(c->gunzip.rec.reserve(2 * (size_t)n_grid));
+        if (int rc = begin()) return rc;
+        HIPCHK(faqcs_launch_gunzip_count(comp, n_comp, piece_bytes, c->gunzip.rec.p, n_grid, 1, c->n_cu, c->compute));
+        if (int rc = end(0)) return rc;
+        return down(grid, c->gunzip.rec.p, sizeof(faqcs_gunzip::Piece) * (size_t)n_grid);
+    }
+    int count_forced(faqcs_gunzip::Piece &pc)
+    {
+        HIPCHK(c->gunzip.one.reserve(2));
+        HIPCHK(hipMemcpyAsync(c->gunzip.one.p, &pc, sizeof pc, hipMemcpyHostToDevice, c->compute));
+        if (int rc = begin()) return rc;
+        HIPCHK(faqcs_launch_gunzip_count(comp, n_comp, piece_bytes, c->gunzip.one.p, 1, 0, c->n_cu, c->compute));
+        if (int rc = end(0)) return rc;
+        return down(&pc, c->gunzip.one.p, sizeof pc);
+    }
+    int write(const std::vector<faqcs_gunzip::ChainPiece> &chain, const std::vector<faqcs_gunzip::MemberRec> &members, uint32_t total,
+              std::vector<faqcs_gunzip::MemberResult> &res)
+    {
+        namespace gz = faqcs_gunzip;
+        std::vector<gz::Slice> slices;
+        gz::make_slices(chain, slices);
+        const size_t n = chain.size(), ns = slices.size();
+        auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
+        const size_t o_slices = n * sizeof(gz::ChainPiece), o_dst = o_slices + ns * sizeof(gz::Slice), o_bad = o_dst + up(4 * n), o_res = o_bad + up(4 * n),
+                     bytes = o_res + up(ns * sizeof(gz::SliceResult));
+        HIPCHK(c->gunzip.rec.reserve(bytes / sizeof(uint4) + 1));
+        HIPCHK(c->gunzip.sym.reserve(((size_t)total * 2 + 15) / sizeof(uint4) + 1));
+        uint8_t *base = (uint8_t *)c->gunzip.rec.p;
+        uint16_t *sym = (uint16_t *)c->gunzip.sym.p;
+        HIPCHK(hipMemcpyAsync(base, chain.data(), n * sizeof(gz::ChainPiece), hipMemcpyHostToDevice, c->compute));
+        if (ns) HIPCHK(hipMemcpyAsync(base + o_slices, slices.data(), ns * sizeof(gz::Slice), hipMemcpyHostToDevice, c->compute));
+        if (int rc = begin()) return rc;
+        HIPCHK(faqcs_launch_gunzip_decode(comp, n_comp, base, (uint32_t)n, sym, (uint32_t *)(base + o_dst), c->n_cu, c->compute));
+        if (int rc = end(1)) return rc;
+        if (int rc = begin()) return rc;
+        HIPCHK(faqcs_launch_gunzip_resolve(base, (uint32_t)n, sym, (uint32_t *)(base + o_bad), c->compute));
+        if (int rc = end(2)) return rc;
+        if (int rc = begin()) return rc;
+        HIPCHK(faqcs_launch_gunzip_narrow(base, base + o_slices, (uint32_t)ns, sym, text, base + o_res, c->n_cu, c->compute));
+        if (int rc = end(1)) return rc;
+        std::vector<uint32_t> dst(n), bad(n);
+        std::vector<gz::SliceResult> sres(ns + 1);
+        if (int rc = down(dst.data(), base + o_dst, 4 * n)) return rc;
+        if (int rc = down(bad.data(), base + o_bad, 4 * n)) return rc;
+        if (ns) if (int rc = down(sres.data(), base + o_res, ns * sizeof(gz::SliceResult))) return rc;
+        gz::fold_results(chain, members, slices, sres.data(), dst.data(), bad.data(), res);
+        return 0;
+    }
+};
+} // namespace
+
+extern "C" int faqcs_gunzip_device(faqcs_ctx *c, const uint8_t *d_comp, uint64_t n_comp, uint32_t piece_bytes, uint32_t max_rounds, const faqcs_gunzip_out *out)
+{
+    if (!c) return fail(FAQCS_E_INVAL, "null ctx");
+    if (int rc = gunzip_check_args("faqcs_gunzip_device", d_comp, n_comp, piece_bytes, out)) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    for (auto &e : c->gunzip.ev) if (!e) HIPCHK(hipEventCreate(&e));
+    c->gunzip.ms[0] = c->gunzip.ms[1] = c->gunzip.ms[2] = 0.0;
+    c->gunzip.timed = false;
+    GunzipDevice B{c, d_comp, (uint32_t)n_comp, piece_bytes ? piece_bytes : faqcs_gunzip::DEFAULT_PIECE, out->text};
+    faqcs_gunzip::Info info;
+    if (int rc = faqcs_gunzip::gunzip_run(B, n_comp, piece_bytes, max_rounds, out->capacity_bytes, info))
+        return rc == faqcs_gunzip::E_RECORD ? fail(FAQCS_E_INVAL, "faqcs_gunzip_device: a piece record that no run produces") : rc;
+    faqcs_gunzip_info h;
+    gunzip_info_out(info, &h);
+    HIPCHK(hipMemcpyAsync(out->info, &h, sizeof h, hipMemcpyHostToDevice, c->compute));
+    HIPCHK(hipStreamSynchronize(c->compute));
+    c->gunzip.timed = true;
+    return 0;
+}
+
+extern "C" int faqcs_gunzip_time_ms(faqcs_ctx *c, double *count_ms, double *decode_ms, double *resolve_ms)
+{
+    if (!c || !count_ms || !decode_ms || !resolve_ms) return fail(FAQCS_E_INVAL, "null argument");
+    if (!c->gunzip.timed) return fail(FAQCS_E_INVAL, "faqcs_gunzip_time_ms: no gunzip on this context yet");
+    *count_ms = c->gunzip.ms[0]; *decode_ms = c->gunzip.ms[1]; *resolve_ms = c->gunzip.ms[2];
+    return 0;
+}
 
 extern "C" int faqcs_deflate_device(faqcs_ctx *c, const uint8_t *d_text, uint64_t n_text, uint32_t member_bytes, int final, const faqcs_deflate_out *out)
 {

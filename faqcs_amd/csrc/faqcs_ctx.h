@@ -1,6 +1,6 @@
 // faqcs_ctx.h -- internal to the host side of libfaqcs_mi.so (never installed): the context every entry point of include/faqcs_mi.h works
 // on, the launch functions of the kernel files, and the few host functions that cross the host side's translation units:
-//   faqcs_host.cpp       host statements and helpers without HIP (faqcs_host.h)     faqcs_capi_seam.hip  emit / parse / render / pair / inflate / deflate / detect
+//   faqcs_host.cpp       host statements and helpers without HIP (faqcs_host.h)     faqcs_capi_seam.hip  emit / parse / render / pair / inflate / gunzip / deflate / detect
 //   faqcs_capi.hip       create / destroy, submission, sync, counters, timing       faqcs_capi_comm.hip  RCCL
 //   faqcs_capi_kmer.hip  k-mer groups, the k-mer tails of a submission, faqcs_kmer_*
 // One faqcs_ctx == the (filter_stats, adapter_stats, PlotInfo, Options) quadruple the reference keeps in
@@ -80,6 +80,10 @@ hipError_t faqcs_launch_render_pair_gather(bool trimmed, const MateDev &m1, cons
 size_t faqcs_inflate_scratch_bytes(uint32_t n_members);
 hipError_t faqcs_launch_inflate_scan(const uint8_t *comp, unsigned long long n_comp, const uint32_t *moff, uint32_t n, const faqcs_inflate_out *out, void *scratch, hipStream_t st);
 hipError_t faqcs_launch_inflate_decode(const uint8_t *comp, const uint32_t *moff, uint32_t n, const faqcs_inflate_out *out, void *scratch, int n_cu, hipStream_t st);
+hipError_t faqcs_launch_gunzip_count(const uint8_t *comp, uint32_t n_comp, uint32_t piece_bytes, void *recs, uint32_t n, int grid_mode, int n_cu, hipStream_t st);
+hipError_t faqcs_launch_gunzip_decode(const uint8_t *comp, uint32_t n_comp, const void *chain, uint32_t n, uint16_t *sym, uint32_t *status, int n_cu, hipStream_t st);
+hipError_t faqcs_launch_gunzip_resolve(const void *chain, uint32_t n, uint16_t *sym, uint32_t *bad, hipStream_t st);
+hipError_t faqcs_launch_gunzip_narrow(const void *chain, const void *slices, uint32_t n_slices, const uint16_t *sym, uint8_t *text, void *results, int n_cu, hipStream_t st);
 size_t faqcs_bgzf_index_scratch_bytes(unsigned long long n_comp);
 hipError_t faqcs_launch_bgzf_index_candidates(const uint8_t *comp, unsigned long long n_comp, void *scratch, int n_cu, hipStream_t st);
 hipError_t faqcs_launch_bgzf_index_chain(const uint8_t *comp, unsigned long long n_comp, int final, uint32_t *member_offset, uint32_t capacity, faqcs_bgzf_index_info *info,
@@ -138,6 +142,16 @@ struct PackStage {
     void release();
 };
 
+// What faqcs_gunzip_device keeps on a context: the records of the pieces, the chain and the slices; one record for a forced start; the 16-bit
+// symbols (2 bytes per text byte); the events around a pass and the three stage times of the last call (faqcs_gunzip_time_ms).
+struct GunzipStage {
+    DevBuf<uint4> rec, one, sym;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    double ms[3] = {0.0, 0.0, 0.0}; // count, decode + narrow, resolve
+    bool timed = false;
+    void release() { rec.release(); one.release(); sym.release(); for (auto &e : ev) if (e) (void)hipEventDestroy(e); }
+};
+
 #pragma GCC visibility pop
 
 struct faqcs_ctx {
@@ -183,6 +197,7 @@ struct faqcs_ctx {
     PackStage inflate; // the header fields, the position and the status of every member, the scan's tile sums | scan, decode
     PackStage bgzf_index; // the candidates' positions, sizes, jump tables and ranks, the tiles' counts | candidates, chain
     PackStage deflate; // every member's slot, size and position, a block's tokens, the scan's tile sums | encode, gather
+    GunzipStage gunzip; // faqcs_gunzip_device: see GunzipStage
     PackStage detect;  // faqcs_detect_device and faqcs_first_error_device: the partial (first hit) of every tile | only the scratch is used: the stage is not timed
     // per-read composition records (trim kernel -> composition_histogram).  Two sets: the histogram kernels of
     // submission k run on the aux stream next to the trim kernel of submission k+1 (LDS-bound next to VALU-bound).

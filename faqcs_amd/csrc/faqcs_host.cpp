@@ -10,6 +10,7 @@
 
 #include "faqcs_host.h"
 #include "faqcs_inflate.h"
+#include "faqcs_gunzip.h"
 #include "faqcs_deflate.h"
 
 static thread_local std::string g_err;
@@ -183,7 +184,11 @@ int render_check_args(const char *who, const faqcs_batch *b, const uint8_t *text
 
 static const char *const INFLATE_TEXT[] = {"", "bgzf: not a BGZF member header", "bgzf: the decoded length differs from ISIZE",
                                            "bgzf: invalid deflate data", "bgzf: the CRC-32 differs from the trailer", "bgzf: the last member is incomplete"};
-extern "C" const char *faqcs_inflate_error_text(int code) { return code >= 0 && code <= FAQCS_INFLATE_E_TRUNCATED ? INFLATE_TEXT[code] : nullptr; }
+extern "C" const char *faqcs_inflate_error_text(int code)
+{
+    if (code == FAQCS_INFLATE_E_SERIAL) return "gzip: the stream does not split into pieces; inflate it on the host";
+    return code >= 0 && code <= FAQCS_INFLATE_E_TRUNCATED ? INFLATE_TEXT[code] : nullptr;
+}
 
 int bgzf_index_check_args(const char *who, const uint8_t *comp, uint64_t n_comp, const uint32_t *member_offset, const faqcs_bgzf_index_info *info)
 {
@@ -255,6 +260,37 @@ extern "C" int faqcs_inflate_host(const uint8_t *comp, uint64_t n_comp, const ui
         }
     }
     *out->info = info;
+    return 0;
+}
+
+int gunzip_check_args(const char *who, const uint8_t *comp, uint64_t n_comp, uint32_t piece_bytes, const faqcs_gunzip_out *out)
+{
+    const std::string w(who);
+    if (!out || !out->text || !out->info) return fail(FAQCS_E_INVAL, w + ": null output, text or info");
+    if (!comp && n_comp) return fail(FAQCS_E_INVAL, w + ": null input");
+    if ((uintptr_t)out->text & 15u) return fail(FAQCS_E_INVAL, w + ": the output text must be 16-byte aligned");
+    if (n_comp >= (1ull << 32)) return fail(FAQCS_E_INVAL, w + ": 2^32 compressed bytes or more in one call");
+    if (piece_bytes && piece_bytes < faqcs_gunzip::MIN_PIECE) return fail(FAQCS_E_INVAL, w + ": a piece is at least 1 024 bytes");
+    return 0;
+}
+
+void gunzip_info_out(const faqcs_gunzip::Info &i, faqcs_gunzip_info *o)
+{
+    o->n_bytes = i.n_bytes; o->consumed = i.consumed; o->n_members = i.n_members; o->overflow = i.overflow; o->error = i.error;
+    o->n_pieces = i.n_pieces; o->n_fixups = i.n_fixups; o->n_rounds = i.n_rounds;
+}
+
+// The host statement of the gunzip rules (include/faqcs_mi.h at faqcs_gunzip_device): the walk and the passes of csrc/faqcs_gunzip.h on one
+// thread, into a buffer of its own first, so that exactly text[0 .. n_bytes) is written.
+extern "C" int faqcs_gunzip_host(const uint8_t *comp, uint64_t n_comp, uint32_t piece_bytes, uint32_t max_rounds, const faqcs_gunzip_out *out)
+{
+    if (int rc = gunzip_check_args("faqcs_gunzip_host", comp, n_comp, piece_bytes, out)) return rc;
+    std::unique_ptr<faqcs_gunzip::HostBackend> B(new faqcs_gunzip::HostBackend(comp, n_comp, piece_bytes));
+    faqcs_gunzip::Info info;
+    if (int rc = faqcs_gunzip::gunzip_run(*B, n_comp, piece_bytes, max_rounds, out->capacity_bytes, info))
+        return rc == faqcs_gunzip::E_RECORD ? fail(FAQCS_E_INVAL, "faqcs_gunzip_host: a piece record that no run produces") : rc;
+    if (!info.overflow && info.n_bytes) memcpy(out->text, B->text.data(), info.n_bytes);
+    gunzip_info_out(info, out->info);
     return 0;
 }
 

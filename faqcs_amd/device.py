@@ -1,6 +1,6 @@
 """Torch-facing helpers of the device seam: inputs and outputs are torch tensors that live on the GPU; the work is the
 library's HIP kernels (faqcs_emit_device, faqcs_render_device, faqcs_pair_device, faqcs_render_pair_device, faqcs_bgzf_index_device, faqcs_inflate_device,
-faqcs_deflate_device, faqcs_detect_device), never torch ops."""
+faqcs_gunzip_device, faqcs_deflate_device, faqcs_detect_device), never torch ops."""
 import ctypes as C
 
 from . import _capi as capi
@@ -266,6 +266,41 @@ def inflated_text(engine, comp, member_offset=None, capacity=None, index="host")
         raise FaqcsError(capi.E_INVAL, "member %d: %s" % (n_mem, engine.lib.faqcs_inflate_error_text(error).decode()))
     a = front + shift
     return o_text[a:a + n_bytes], o_off[:n_mem + 1]
+
+
+def gunzipped_text(engine, comp, capacity=None, piece_bytes=0, max_rounds=0):
+    """The text of ordinary gzip input, inflated by pieces on the device (faqcs_gunzip_device); the call blocks.
+
+    comp: uint8 CUDA tensor, the compressed bytes (one or more whole gzip members -- gzip, pigz, bgzip output alike; any alignment);
+    capacity: bytes of text to make room for (default: four times the compressed bytes, and the call is repeated once with what info
+    asks for when that is too little); piece_bytes / max_rounds: 0 for the defaults.  Returns the text: uint8 [n_bytes] -- a view that
+    starts 16-byte aligned, 64 bytes into its storage, with 64 spare bytes behind: a valid d_text for faqcs_parse_device().  A bad member
+    raises FaqcsError with the member's index and faqcs_inflate_error_text (capi.INFLATE_E_SERIAL: inflate this input on the host)."""
+    import torch
+
+    dev = comp.device
+    comp = comp.contiguous()
+    n_comp = int(comp.numel())
+    cap = 4 * n_comp + 4096 if capacity is None else int(capacity)
+    front = 64
+    info = torch.zeros(5, dtype=torch.int64, device=dev)
+    torch.cuda.current_stream(dev).synchronize()  # the library's compute stream is its own: the input must be complete
+    for attempt in range(2):
+        o_text = torch.empty(front + cap + capi.ARENA_PAD_AFTER + 16, dtype=torch.uint8, device=dev)
+        shift = (-(o_text.data_ptr() + front)) % 16
+        out = capi.GunzipOut(o_text.data_ptr() + front + shift, cap, info.data_ptr())
+        torch.cuda.current_stream(dev).synchronize()
+        engine.gunzip_device(comp.data_ptr() if n_comp else None, n_comp, out, piece_bytes, max_rounds)
+        p = capi.GunzipInfo.from_buffer_copy(info.cpu().numpy().tobytes())
+        if not p.overflow:
+            break
+        if attempt or p.n_bytes >= 1 << 32:
+            raise FaqcsError(capi.E_INVAL, "faqcs_gunzip_device: the text needs %d bytes, the output holds %d" % (p.n_bytes, cap))
+        cap = int(p.n_bytes)
+    if p.error:
+        raise FaqcsError(capi.E_INVAL, "member %d: %s" % (p.n_members, engine.lib.faqcs_inflate_error_text(p.error).decode()))
+    a = front + shift
+    return o_text[a:a + int(p.n_bytes)]
 
 
 def deflated_bgzf(engine, text, member_bytes=0, final=True, capacity=None, mode=capi.DEFLATE_FAST):

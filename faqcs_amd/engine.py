@@ -39,6 +39,26 @@ def bgzf_index_host(comp, final=True, lib=None):
     return off[:info.n_members + 1].copy(), int(info.consumed), int(info.error)
 
 
+def gunzip_host(comp, piece_bytes=0, max_rounds=0, capacity=None, lib=None):
+    """faqcs_gunzip_host (host only, no GPU): ordinary gzip `comp` (bytes or a uint8 array; one or more whole members) inflated by pieces of
+    piece_bytes compressed bytes (0: the default), with at most max_rounds count rounds per member (0: the default).  capacity: bytes of text
+    to make room for (default: found with a first call).  Returns (text bytes, info dict): the faqcs_gunzip_info fields -- what
+    faqcs_gunzip_device states for the same bytes, field for field; with info["overflow"] the text is empty."""
+    lib = lib or capi.load_library()
+    buf = np.frombuffer(comp, dtype=np.uint8) if isinstance(comp, (bytes, bytearray, memoryview)) else np.ascontiguousarray(comp, dtype=np.uint8)
+    info = capi.GunzipInfo()
+    for cap in ([0, None] if capacity is None else [int(capacity)]):
+        cap = int(info.n_bytes) if cap is None else cap
+        store = np.zeros(cap + 32, dtype=np.uint8)
+        shift = (-store.ctypes.data) % 16
+        out = capi.GunzipOut(store.ctypes.data + shift, cap, C.addressof(info))
+        _check(lib, lib.faqcs_gunzip_host(buf.ctypes.data if len(buf) else None, len(buf), int(piece_bytes), int(max_rounds), C.byref(out)))
+        if not info.overflow:
+            break
+    d = {f: int(getattr(info, f)) for f, _ in capi.GunzipInfo._fields_}
+    return (b"" if info.overflow else store[shift:shift + info.n_bytes].tobytes()), d
+
+
 def deflate_host(text, member_bytes=0, final=True, lib=None, mode=capi.DEFLATE_FAST):
     """faqcs_deflate_host_mode (host only, no GPU; mode: capi.DEFLATE_FAST, what faqcs_deflate_host does, or capi.DEFLATE_DENSE): `text` (bytes or a uint8 array) as BGZF members of member_bytes bytes of text each (0: 65 280),
     the EOF member behind them when final.  Returns (comp bytes, member_offset uint32 [n_members + 1], n_stored): the bytes
@@ -206,6 +226,22 @@ class HipEngine:
         a, g = C.c_double(), C.c_double()
         _check(self.lib, self.lib.faqcs_deflate_time_ms(self.ctx, C.byref(a), C.byref(g)))
         return a.value, g.value
+
+    def gunzip_device(self, d_comp, n_comp, out, piece_bytes=0, max_rounds=0):
+        """faqcs_gunzip_device: ordinary gzip in device memory (d_comp: device address, any alignment; whole members) -> its text in the
+        arrays of `out` (a capi.GunzipOut of device pointers).  Unlike the other seam calls this one BLOCKS: text and info are complete
+        when it returns."""
+        _check(self.lib, self.lib.faqcs_gunzip_device(self.ctx, d_comp, int(n_comp), int(piece_bytes), int(max_rounds), C.byref(out)))
+
+    def gunzip_time_ms(self):
+        """(count ms, decode ms, resolve ms) of the last gunzip_device() on this engine (HIP events on the compute stream)."""
+        a, g, r = C.c_double(), C.c_double(), C.c_double()
+        _check(self.lib, self.lib.faqcs_gunzip_time_ms(self.ctx, C.byref(a), C.byref(g), C.byref(r)))
+        return a.value, g.value, r.value
+
+    def gunzip_host(self, comp, piece_bytes=0, max_rounds=0, capacity=None):
+        """gunzip_host() of this module on the engine's library."""
+        return gunzip_host(comp, piece_bytes, max_rounds, capacity, self.lib)
 
     def bgzf_index_device(self, d_comp, n_comp, final, d_member_offset, capacity_members, d_info):
         """faqcs_bgzf_index_device: where the BGZF members of compressed bytes in device memory are (d_comp: device address, any alignment)

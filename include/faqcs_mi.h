@@ -35,6 +35,7 @@ extern "C" {
  * faqcs_emit_device (the trimmed, edited reads packed on the device) is a new entry point with structures of its own, and so are
  * faqcs_parse_device / faqcs_parse_host (FASTQ text to a packed batch) and faqcs_render_device / faqcs_render_host (the FASTQ text of the
  * output files), and faqcs_inflate_device / faqcs_inflate_host / faqcs_bgzf_index_host / faqcs_bgzf_index_device (BGZF members to that text),
+ * and faqcs_gunzip_device / faqcs_gunzip_host (ordinary gzip to that text; FAQCS_INFLATE_E_SERIAL is theirs alone),
  * and faqcs_deflate_device / faqcs_deflate_host (text to BGZF members), and faqcs_pair_device / faqcs_pair_host /
  * faqcs_render_pair_device / faqcs_render_pair_host (the two mates of a paired run from two batches), and faqcs_detect_device /
  * faqcs_detect_host / faqcs_first_error_device / faqcs_first_error_host / faqcs_set_input_quality_offset (the decisions around trim()). */
@@ -424,7 +425,7 @@ int  faqcs_render_pair_host(const faqcs_params *p, int file, const faqcs_mate *m
                             const uint8_t *route, uint32_t n_pairs, const faqcs_render_out *out);
 
 /* The step in front of the device seam: compressed input.  BGZF (bgzip) members in device memory -> the FASTQ text faqcs_parse_device()
- * takes.  Ordinary single-stream gzip is not taken: it has no member boundaries (the command line's faqcs_pargz.h handles it on the host).
+ * takes.  Ordinary gzip -- members of any size, no index -- is faqcs_gunzip_device's, below.
  * A MEMBER:
  *   - a gzip member whose header has ID1 ID2 CM = 1f 8b 08 and FLG.FEXTRA set, and whose extra field holds a 'B' 'C' subfield of length 2:
  *     BSIZE, the member's total size - 1.  The acceptance rule is that of the command line's reader (BgzfReader::member_size): subfields in
@@ -490,7 +491,8 @@ int  faqcs_render_pair_host(const faqcs_params *p, int file, const faqcs_mate *m
  *   demand, freed by faqcs_destroy().
  * faqcs_inflate_host is the same call with HOST pointers: the host statement of these rules, single-threaded, no HIP call and no zlib,
  * built from the same decoder text as the kernel (csrc/faqcs_inflate.h).  It writes exactly text[0 .. n_bytes). */
-enum { FAQCS_INFLATE_OK = 0, FAQCS_INFLATE_E_HEADER, FAQCS_INFLATE_E_LENGTH, FAQCS_INFLATE_E_DATA, FAQCS_INFLATE_E_CRC, FAQCS_INFLATE_E_TRUNCATED };
+enum { FAQCS_INFLATE_OK = 0, FAQCS_INFLATE_E_HEADER, FAQCS_INFLATE_E_LENGTH, FAQCS_INFLATE_E_DATA, FAQCS_INFLATE_E_CRC, FAQCS_INFLATE_E_TRUNCATED,
+       FAQCS_INFLATE_E_SERIAL = 16 /* faqcs_gunzip_device only, and no property of the data: the stream does not split (6 .. 15 are no codes) */ };
 const char *faqcs_inflate_error_text(int code);   /* "" for FAQCS_INFLATE_OK, NULL for no code */
 
 typedef struct faqcs_bgzf_index_info {
@@ -522,6 +524,58 @@ typedef struct faqcs_inflate_out {
 int  faqcs_inflate_device(faqcs_ctx *ctx, const uint8_t *d_comp, uint64_t n_comp, const uint32_t *d_member_offset, uint32_t n_members,
                           const faqcs_inflate_out *out);
 int  faqcs_inflate_host(const uint8_t *comp, uint64_t n_comp, const uint32_t *member_offset, uint32_t n_members, const faqcs_inflate_out *out);
+
+/* Ordinary gzip in device memory -> the same text: the files users actually have (gzip, pigz, bgzip output alike), which carry no index.
+ * The text is what zlib's gzread delivers.
+ *   input         d_comp[0 .. n_comp) holds one or more COMPLETE RFC 1952 members, with any FLG fields: FEXTRA, FNAME and FCOMMENT are
+ *                 skipped, FHCRC is skipped and not verified; a reserved FLG bit or CM != 8 is E_HEADER.  BGZF members are ordinary members
+ *                 here.  A member's window starts empty: a distance that reaches in front of the member is E_DATA.  Code sets are accepted
+ *                 as faqcs_inflate_device accepts them.  No alignment is asked of d_comp; nothing outside d_comp[0 .. n_comp) is read.
+ *   end of data   bytes behind the last member that do not start 1f 8b end the data without an error (consumed = n_comp), as for gzread and
+ *                 faqcs_bgzf_index_host.  A last member whose header, stream or trailer is incomplete is E_TRUNCATED with consumed at its
+ *                 header: there is no final = 0 in this version, a member must be resident whole.
+ *   errors        per member and sequential, as in faqcs_inflate_device: the first bad member in input order decides, n_members is its index,
+ *                 consumed where its header starts, n_bytes the text of the members in front of it, and that text is delivered byte-exact
+ *                 (what lies behind it in `text` is unspecified).  E_DATA: an invalid code or code set, block type 3, LEN != ~NLEN, a
+ *                 distance in front of the member.  E_LENGTH (ISIZE is the length modulo 2^32) and then E_CRC are looked at last.
+ *   capacity      the total text is known before anything is written.  total > capacity_bytes or total >= 2^32: overflow = 1; n_bytes,
+ *                 n_members and consumed are those of the members whose streams were walked whole, error is what ended the walk (0, or the
+ *                 E_HEADER / E_DATA / E_TRUNCATED / E_SERIAL of member n_members), and NOTHING but info is written.
+ *   the scheme     the compressed bytes are cut every piece_bytes bytes (0: 65 536; at least 1 024; small values
+ *                 exist so that tests cross many piece edges with little data).  A wave per piece probes its range for the first bit
+ *                 position that can begin a dynamic-Huffman block and counts, without output, up to the first block end at or behind its
+ *                 range end.  The host walks these records from each member's first block: a piece whose start is not where the chain arrives
+ *                 is counted again from there, in a round of its own.  max_rounds (0: 32) bounds the rounds spent inside ONE member; a member
+ *                 that needs more is FAQCS_INFLATE_E_SERIAL -- "this stream does not split (stored or fixed blocks only, blocks that no
+ *                 probe finds); inflate it on the host" -- an error of that member like any other: defined, bounded, never a wrong text.
+ *                 Then the pieces of the chain are decoded to 16-bit symbols -- a byte, or a marker for a byte of the 32 768 in front of
+ *                 the piece --, the markers are resolved over the chain in order, and the symbols become text, with a CRC-32 per slice.
+ *   info          n_pieces (pieces of the chain), n_fixups (starts the chain had to force inside a member) and n_rounds (count rounds) say
+ *                 what the speculation did.  They are part of the contract: the host statement takes the same decisions and states the same.
+ *   THE CALL BLOCKS.  Unlike the other seam calls this one is a short conversation between host and device -- a few bytes per piece come
+ *   back for the walk, per round -- on the context's compute stream; when it returns, the text and info are complete.  d_comp, out->text and
+ *   out->info are DEVICE pointers all the same.  out->text is 16-byte aligned; the kernels write text[0 .. total) and info, nothing else; with
+ *   the arena pads the caller leaves, (text, n_bytes) is a valid d_text for faqcs_parse_device().
+ *   FAQCS_E_INVAL: n_comp >= 2^32, 0 < piece_bytes < 1 024, a null ctx / out / out->text / out->info, a null d_comp with n_comp > 0, out->text
+ *   not 16-byte aligned.  Scratch is the library's, grown on demand and freed by faqcs_destroy(): 2 bytes per text byte (the symbols), and
+ *   32 bytes per piece + 24 bytes per 16 KiB of text (the records).
+ * faqcs_gunzip_host is the same call with HOST pointers: the host statement of these rules, single-threaded, no HIP call and no zlib, built
+ * from the same text as the kernels (csrc/faqcs_gunzip.h).  It writes exactly text[0 .. n_bytes). */
+typedef struct faqcs_gunzip_info {
+    uint64_t n_bytes;      /* text of the members in front of the first bad one (all of them when error == 0) */
+    uint64_t consumed;     /* compressed bytes covered by those members (data that ends without an error: n_comp) */
+    uint32_t n_members;    /* members delivered (== index of the bad member when error != 0) */
+    uint32_t overflow;     /* 1: the total > capacity_bytes or >= 2^32 */
+    int32_t  error;        /* FAQCS_INFLATE_* of member n_members */
+    uint32_t n_pieces, n_fixups, n_rounds;   /* what the speculation did */
+} faqcs_gunzip_info;
+typedef struct faqcs_gunzip_out {
+    uint8_t  *text;                /* 16-byte aligned; capacity_bytes (+ FAQCS_ARENA_PAD_AFTER for faqcs_parse_device) */
+    uint64_t  capacity_bytes;
+    faqcs_gunzip_info *info;
+} faqcs_gunzip_out;
+int  faqcs_gunzip_device(faqcs_ctx *ctx, const uint8_t *d_comp, uint64_t n_comp, uint32_t piece_bytes, uint32_t max_rounds, const faqcs_gunzip_out *out);
+int  faqcs_gunzip_host(const uint8_t *comp, uint64_t n_comp, uint32_t piece_bytes, uint32_t max_rounds, const faqcs_gunzip_out *out);
 
 /* The step behind the device seam: compressed output.  Text in device memory (what faqcs_render_device() assembled, or any bytes) -> BGZF
  * members in device memory, so that a third of the bytes leave the card and the result is what faqcs_inflate_device() takes.
@@ -789,6 +843,9 @@ int  faqcs_pair_time_ms(faqcs_ctx *ctx, double *check_ms, double *finish_ms);
 int  faqcs_render_pair_time_ms(faqcs_ctx *ctx, double *scan_ms, double *gather_ms);
 /* the same for the LAST faqcs_inflate_device() on the context: the scan of the headers (scan_ms), the decode with its CRC and the status (decode_ms) */
 int  faqcs_inflate_time_ms(faqcs_ctx *ctx, double *scan_ms, double *decode_ms);
+/* the same for the LAST faqcs_gunzip_device() on the context: every count round (count_ms), the decode pass and the narrowing with its CRC
+ * (decode_ms), the resolve pass -- the serial part, one step per piece -- (resolve_ms) */
+int  faqcs_gunzip_time_ms(faqcs_ctx *ctx, double *count_ms, double *decode_ms, double *resolve_ms);
 /* the same for the LAST faqcs_deflate_device() on the context: the members' encoding into their slots (encode_ms), sizes, positions and the gather (gather_ms) */
 int  faqcs_deflate_time_ms(faqcs_ctx *ctx, double *encode_ms, double *gather_ms);
 /* diagnostic builds only: section clocks accumulated by the trim kernel (16 words; read and cleared) */
