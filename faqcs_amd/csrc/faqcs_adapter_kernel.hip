@@ -35,6 +35,9 @@ struct AdapterDev {
     float match_rate;        // float(1.0 - filterAdapterMismatchRate), trim.cpp:969
     uint32_t longest;        // (host copies) bases of the longest adapter, dwords of `planes`: what picks the kernel variant
     uint32_t plane_dwords;
+    uint32_t has_gap;        // some target of the library holds a '-' (mask 16, seq_overlap.h:138).  A '-' in a read matches it (16 & 16 > 0,
+                             // seq_overlap.cpp:157-161) and the four base planes do not see that, so their match counts are no bounds for such a
+                             // library: it runs without the prefilter, the pair kernel and the bound pass -- every target through the per-cell aligner
 };
 
 // seq_overlap.cpp:372-411 na_to_bits() as a table over 'a'..'z' (case folded); 0 == the reference throws
@@ -226,7 +229,7 @@ __global__ __launch_bounds__(NW * 64, MAXLEN == 320 ? 3 : (MAXLEN == 256 ? FAQCS
     bool has_long = false; // some adapter takes the sliding long-target prefilter
     for (uint32_t i = 0; i < A.n_adapters; ++i) has_long = has_long || (int)s_meta[i].x > 128;
     has_long = uni((int)has_long) != 0;
-    const bool prefilter_on = uni((int)((dbg & 8u) == 0u)) != 0;
+    const bool prefilter_on = uni((int)((dbg & 8u) == 0u && A.has_gap == 0u)) != 0;
 
     // A wave takes chunks of 64 consecutive reads: offsets load and results store as one coalesced vector per chunk,
     // per-read scalars come out of the lanes with v_readlane, and the bases of read t+1 are fetched while read t is
@@ -324,7 +327,7 @@ __global__ __launch_bounds__(NW * 64, MAXLEN == 320 ? 3 : (MAXLEN == 256 ? FAQCS
             // bound is aligned first; a block whose bound is below the best score so far cannot win (ties are decided by
             // the explicit (M, i, j) comparison below, so the visiting order is free).  (GROUPED: a target of more than BB_CAP blocks is
             // aligned unpruned -- diagonals are independent, so the result is the same.)
-            const bool pruned = MAXLEN <= 320 && tpl_cached && !outside && (!GROUPED || ndiag <= 64 * BB_CAP);
+            const bool pruned = MAXLEN <= 320 && tpl_cached && !outside && (!GROUPED || ndiag <= 64 * BB_CAP) && A.has_gap == 0u;
             constexpr int NBX = MAXLEN == 320 ? 7 : 6, NAX = NBX + 1; // window blocks / accumulators of the sliding bound pass
             uint32_t *bb = s_bb[wave];
             int first_block = 0;
@@ -1423,7 +1426,7 @@ static hipError_t launch_adapter(const AdapterDev &A, const AdapterGroup &G, con
     // two reads per wave (round 6): reads of up to 160 bases, at most 32 adapters of at most 128 bases whose planes fit the LDS copy;
     // FAQCS_ADAPTER_PAIR=0 keeps adapter_overlap for them (A/B).  (Not for a group of a larger library: the pair kernel carries no state.)
     static const bool pair_on = [] { const char *e = getenv("FAQCS_ADAPTER_PAIR"); return !e || atoi(e) != 0; }();
-    if (!GROUPED && pair_on && max_len <= 160 && A.n_adapters <= 32 && A.longest <= 128 && A.plane_dwords <= 4096 && (dbg & 8u) == 0u) {
+    if (!GROUPED && pair_on && max_len <= 160 && A.n_adapters <= 32 && A.longest <= 128 && A.plane_dwords <= 4096 && (dbg & 8u) == 0u && A.has_gap == 0u) {
         constexpr int NW = 4;
         uint32_t grid = (n_reads + 64 * NW - 1) / (64 * NW);
         const uint32_t cap = (uint32_t)n_cu * 8u;

@@ -140,6 +140,7 @@ extern "C" int faqcs_create(const faqcs_params *p, int device_id, faqcs_ctx **ou
             for (size_t k = 0; k < L; ++k) {
                 const uint8_t b = na_to_bits_host(s[k]);
                 if (!b) return fail(FAQCS_E_BASE, "seq_overlap.cpp:na_to_bits: Unknown base!");
+                if (b == 16) c->adapter_has_gap = 1u;
                 bits.push_back(b);
             }
             start.push_back((uint32_t)bits.size());
@@ -316,7 +317,8 @@ static int enqueue_adapter(faqcs_ctx *c, Timing &t, const Submission &s)
                                     c->d_counters + c->lay.adapter_stats, c->d_err, c->dp.dbg, c->n_cu, c->compute);
     };
     if (c->agroups.empty()) {
-        AdapterDev A{c->d_abits, c->d_astart, c->d_aplanes, c->d_awstart, c->prm.n_adapters, c->match_rate, c->adapter_longest, c->adapter_plane_dwords};
+        AdapterDev A{c->d_abits, c->d_astart, c->d_aplanes, c->d_awstart, c->prm.n_adapters, c->match_rate, c->adapter_longest, c->adapter_plane_dwords,
+                     c->adapter_has_gap};
         HIPCHK(launch(A, nullptr));
         return 0;
     }
@@ -329,7 +331,7 @@ static int enqueue_adapter(faqcs_ctx *c, Timing &t, const Submission &s)
     for (size_t k = 0; k < c->agroups.size(); ++k) {
         const faqcs_ctx::AdapterGroupHost &g = c->agroups[k];
         AdapterDev A{c->d_abits, c->d_astart + g.j0, c->d_aplanes + 4 * (size_t)g.w0, c->d_awstart_grp + g.j0 + k, g.n, c->match_rate,
-                     g.longest, g.plane_dwords};
+                     g.longest, g.plane_dwords, c->adapter_has_gap};
         G.j0 = g.j0; G.last = k + 1 == c->agroups.size() ? 1u : 0u;
         HIPCHK(launch(A, &G));
     }

@@ -31,7 +31,7 @@ struct AdapterDev { // (field by field in faqcs_adapter_kernel.hip)
     const uint32_t *start, *planes, *wstart;
     uint32_t n_adapters;
     float match_rate;
-    uint32_t longest, plane_dwords;
+    uint32_t longest, plane_dwords, has_gap;
 };
 // the trim launchers, one per kernel file: each executes a TrimPlan (trim_plan(), faqcs_trim_plan.h) that names its kernel
 hipError_t faqcs_launch_trim_lds(const TrimPlan &plan, const DevParams &P, const TrimArgs &a);
@@ -174,6 +174,7 @@ struct faqcs_ctx {
     uint32_t *d_astart = nullptr, *d_aplanes = nullptr, *d_awstart = nullptr;
     float match_rate = 0.f;
     uint32_t adapter_longest = 0, adapter_plane_dwords = 0;
+    uint32_t adapter_has_gap = 0; // a target holds a '-': the base planes' counts bound nothing (AdapterDev::has_gap)
     // a library of more than FAQCS_ADAPTER_GROUP targets, or with a target of more than FAQCS_ADAPTER_SINGLE_LENGTH bases: consecutive groups
     // of targets, one adapter_overlap launch each, that carry every read's state in s_astate / s_amask (faqcs_dev.h); empty: one pass
     struct AdapterGroupHost { uint32_t j0, n, w0, longest, plane_dwords; };
