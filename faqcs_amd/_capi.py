@@ -139,6 +139,17 @@ class GunzipOut(C.Structure):
 
 GUNZIP_DEFAULT_PIECE, GUNZIP_DEFAULT_ROUNDS = 64 << 10, 32  # what piece_bytes = 0 and max_rounds = 0 mean
 
+# FAQCS_GUNZIP_*: faqcs_gunzip_state.phase, what the next call's first byte is
+GUNZIP_BETWEEN, GUNZIP_STREAM, GUNZIP_TRAILER = range(3)
+GUNZIP_WINDOW = 32768  # bytes of faqcs_gunzip_state.window
+
+
+class GunzipState(C.Structure):
+    """faqcs_gunzip_state: what faqcs_gunzip_stream_device / _host carry from one call on a file to the next.  Host memory; all zero but
+    `window` (device memory for _device, host memory for _host) before a file's first call."""
+    _fields_ = [("member_bytes", C.c_uint64), ("total_bytes", C.c_uint64), ("total_comp", C.c_uint64), ("phase", C.c_uint32), ("bit", C.c_uint32),
+                ("crc", C.c_uint32), ("window_bytes", C.c_uint32), ("members", C.c_uint32), ("reserved", C.c_uint32), ("window", C.c_void_p)]
+
 
 class DeflateInfo(C.Structure):
     """faqcs_deflate_info: what the members need (always), whether they fitted, and how many of them hold a stored block."""
@@ -282,6 +293,8 @@ def load_library():
         "faqcs_inflate_time_ms": (i32, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "faqcs_gunzip_device": (i32, [vp, vp, u64, u32, u32, C.POINTER(GunzipOut)]),
         "faqcs_gunzip_host": (i32, [vp, u64, u32, u32, C.POINTER(GunzipOut)]),
+        "faqcs_gunzip_stream_device": (i32, [vp, vp, u64, i32, u32, u32, C.POINTER(GunzipState), C.POINTER(GunzipOut)]),
+        "faqcs_gunzip_stream_host": (i32, [vp, u64, i32, u32, u32, C.POINTER(GunzipState), C.POINTER(GunzipOut)]),
         "faqcs_gunzip_time_ms": (i32, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "faqcs_deflate_device": (i32, [vp, vp, u64, u32, i32, C.POINTER(DeflateOut)]),
         "faqcs_deflate_host": (i32, [vp, u64, u32, i32, C.POINTER(DeflateOut)]),

@@ -165,6 +165,7 @@ struct GunzipDevice {
     const uint8_t *comp;
     uint32_t n_comp, piece_bytes;
     uint8_t *text;
+    uint8_t *window; // faqcs_gunzip_stream_device: the caller's 32 768 bytes in device memory
     int down(void *dst, const void *src, size_t n)
     {
         HIPCHK(hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, c->compute));
@@ -199,8 +200,8 @@ struct GunzipDevice {
         if (int rc = end(0)) return rc;
         return down(&pc, c->gunzip.one.p, sizeof pc);
     }
-    int write(const std::vector<faqcs_gunzip::ChainPiece> &chain, const std::vector<faqcs_gunzip::MemberRec> &members, uint32_t total,
-              std::vector<faqcs_gunzip::MemberResult> &res)
+    int write(const std::vector<faqcs_gunzip::ChainPiece> &chain, const std::vector<faqcs_gunzip::MemberRec> &members, uint32_t front, uint32_t window_bytes,
+              uint32_t total, std::vector<faqcs_gunzip::MemberResult> &res)
     {
         namespace gz = faqcs_gunzip;
         std::vector<gz::Slice> slices;
@@ -210,19 +211,20 @@ struct GunzipDevice {
         const size_t o_slices = n * sizeof(gz::ChainPiece), o_dst = o_slices + ns * sizeof(gz::Slice), o_bad = o_dst + up(4 * n), o_res = o_bad + up(4 * n),
                      bytes = o_res + up(ns * sizeof(gz::SliceResult));
         HIPCHK(c->gunzip.rec.reserve(bytes / sizeof(uint4) + 1));
-        HIPCHK(c->gunzip.sym.reserve(((size_t)total * 2 + 15) / sizeof(uint4) + 1));
+        HIPCHK(c->gunzip.sym.reserve((((size_t)front + total) * 2 + 15) / sizeof(uint4) + 1));
         uint8_t *base = (uint8_t *)c->gunzip.rec.p;
         uint16_t *sym = (uint16_t *)c->gunzip.sym.p;
         HIPCHK(hipMemcpyAsync(base, chain.data(), n * sizeof(gz::ChainPiece), hipMemcpyHostToDevice, c->compute));
         if (ns) HIPCHK(hipMemcpyAsync(base + o_slices, slices.data(), ns * sizeof(gz::Slice), hipMemcpyHostToDevice, c->compute));
         if (int rc = begin()) return rc;
+        HIPCHK(faqcs_launch_gunzip_window_load(window, window_bytes, sym, c->compute));
         HIPCHK(faqcs_launch_gunzip_decode(comp, n_comp, base, (uint32_t)n, sym, (uint32_t *)(base + o_dst), c->n_cu, c->compute));
         if (int rc = end(1)) return rc;
         if (int rc = begin()) return rc;
         HIPCHK(faqcs_launch_gunzip_resolve(base, (uint32_t)n, sym, (uint32_t *)(base + o_bad), c->compute));
         if (int rc = end(2)) return rc;
         if (int rc = begin()) return rc;
-        HIPCHK(faqcs_launch_gunzip_narrow(base, base + o_slices, (uint32_t)ns, sym, text, base + o_res, c->n_cu, c->compute));
+        HIPCHK(faqcs_launch_gunzip_narrow(base, base + o_slices, (uint32_t)ns, sym, text, front, base + o_res, c->n_cu, c->compute));
         if (int rc = end(1)) return rc;
         std::vector<uint32_t> dst(n), bad(n);
         std::vector<gz::SliceResult> sres(ns + 1);
@@ -232,27 +234,52 @@ struct GunzipDevice {
         gz::fold_results(chain, members, slices, sres.data(), dst.data(), bad.data(), res);
         return 0;
     }
+    int window_save(uint32_t take_old, uint32_t take_new, uint32_t text_end)
+    {
+        if (int rc = begin()) return rc;
+        HIPCHK(faqcs_launch_gunzip_window_save((const uint16_t *)c->gunzip.sym.p, text, take_old, take_new, text_end, window, c->compute));
+        return end(1);
+    }
 };
 } // namespace
+
+// both device entry points behind their argument checks; state == nullptr: the single call
+static int gunzip_on_device(const char *who, faqcs_ctx *c, const uint8_t *d_comp, uint64_t n_comp, int final, uint32_t piece_bytes, uint32_t max_rounds,
+                            faqcs_gunzip_state *state, const faqcs_gunzip_out *out)
+{
+    HIPCHK(hipSetDevice(c->device));
+    for (auto &e : c->gunzip.ev) if (!e) HIPCHK(hipEventCreate(&e));
+    c->gunzip.ms[0] = c->gunzip.ms[1] = c->gunzip.ms[2] = 0.0;
+    c->gunzip.timed = false;
+    GunzipDevice B{c, d_comp, (uint32_t)n_comp, piece_bytes ? piece_bytes : faqcs_gunzip::DEFAULT_PIECE, out->text, state ? state->window : nullptr};
+    faqcs_gunzip::Info info;
+    faqcs_gunzip::State st{};
+    if (state) gunzip_state_in(state, &st);
+    if (int rc = faqcs_gunzip::gunzip_run(B, n_comp, piece_bytes, max_rounds, out->capacity_bytes, info, state ? &st : nullptr, final != 0))
+        return rc == faqcs_gunzip::E_RECORD ? fail(FAQCS_E_INVAL, std::string(who) + ": a piece record that no run produces") : rc;
+    faqcs_gunzip_info h;
+    gunzip_info_out(info, &h);
+    HIPCHK(hipMemcpyAsync(out->info, &h, sizeof h, hipMemcpyHostToDevice, c->compute));
+    HIPCHK(hipStreamSynchronize(c->compute));
+    if (state) gunzip_state_out(st, state);
+    c->gunzip.timed = true;
+    return 0;
+}
 
 extern "C" int faqcs_gunzip_device(faqcs_ctx *c, const uint8_t *d_comp, uint64_t n_comp, uint32_t piece_bytes, uint32_t max_rounds, const faqcs_gunzip_out *out)
 {
     if (!c) return fail(FAQCS_E_INVAL, "null ctx");
     if (int rc = gunzip_check_args("faqcs_gunzip_device", d_comp, n_comp, piece_bytes, out)) return rc;
-    HIPCHK(hipSetDevice(c->device));
-    for (auto &e : c->gunzip.ev) if (!e) HIPCHK(hipEventCreate(&e));
-    c->gunzip.ms[0] = c->gunzip.ms[1] = c->gunzip.ms[2] = 0.0;
-    c->gunzip.timed = false;
-    GunzipDevice B{c, d_comp, (uint32_t)n_comp, piece_bytes ? piece_bytes : faqcs_gunzip::DEFAULT_PIECE, out->text};
-    faqcs_gunzip::Info info;
-    if (int rc = faqcs_gunzip::gunzip_run(B, n_comp, piece_bytes, max_rounds, out->capacity_bytes, info))
-        return rc == faqcs_gunzip::E_RECORD ? fail(FAQCS_E_INVAL, "faqcs_gunzip_device: a piece record that no run produces") : rc;
-    faqcs_gunzip_info h;
-    gunzip_info_out(info, &h);
-    HIPCHK(hipMemcpyAsync(out->info, &h, sizeof h, hipMemcpyHostToDevice, c->compute));
-    HIPCHK(hipStreamSynchronize(c->compute));
-    c->gunzip.timed = true;
-    return 0;
+    return gunzip_on_device("faqcs_gunzip_device", c, d_comp, n_comp, 1, piece_bytes, max_rounds, nullptr, out);
+}
+
+extern "C" int faqcs_gunzip_stream_device(faqcs_ctx *c, const uint8_t *d_comp, uint64_t n_comp, int final, uint32_t piece_bytes, uint32_t max_rounds,
+                                          faqcs_gunzip_state *state, const faqcs_gunzip_out *out)
+{
+    if (!c) return fail(FAQCS_E_INVAL, "null ctx");
+    if (int rc = gunzip_check_args("faqcs_gunzip_stream_device", d_comp, n_comp, piece_bytes, out)) return rc;
+    if (int rc = gunzip_state_check_args("faqcs_gunzip_stream_device", state)) return rc;
+    return gunzip_on_device("faqcs_gunzip_stream_device", c, d_comp, n_comp, final, piece_bytes, max_rounds, state, out);
 }
 
 extern "C" int faqcs_gunzip_time_ms(faqcs_ctx *c, double *count_ms, double *decode_ms, double *resolve_ms)

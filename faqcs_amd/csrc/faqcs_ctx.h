@@ -83,7 +83,10 @@ hipError_t faqcs_launch_inflate_decode(const uint8_t *comp, const uint32_t *moff
 hipError_t faqcs_launch_gunzip_count(const uint8_t *comp, uint32_t n_comp, uint32_t piece_bytes, void *recs, uint32_t n, int grid_mode, int n_cu, hipStream_t st);
 hipError_t faqcs_launch_gunzip_decode(const uint8_t *comp, uint32_t n_comp, const void *chain, uint32_t n, uint16_t *sym, uint32_t *status, int n_cu, hipStream_t st);
 hipError_t faqcs_launch_gunzip_resolve(const void *chain, uint32_t n, uint16_t *sym, uint32_t *bad, hipStream_t st);
-hipError_t faqcs_launch_gunzip_narrow(const void *chain, const void *slices, uint32_t n_slices, const uint16_t *sym, uint8_t *text, void *results, int n_cu, hipStream_t st);
+hipError_t faqcs_launch_gunzip_narrow(const void *chain, const void *slices, uint32_t n_slices, const uint16_t *sym, uint8_t *text, uint32_t front, void *results, int n_cu,
+                                      hipStream_t st);
+hipError_t faqcs_launch_gunzip_window_load(const uint8_t *window, uint32_t window_bytes, uint16_t *sym, hipStream_t st);
+hipError_t faqcs_launch_gunzip_window_save(const uint16_t *sym, const uint8_t *text, uint32_t take_old, uint32_t take_new, uint32_t text_end, uint8_t *window, hipStream_t st);
 size_t faqcs_bgzf_index_scratch_bytes(unsigned long long n_comp);
 hipError_t faqcs_launch_bgzf_index_candidates(const uint8_t *comp, unsigned long long n_comp, void *scratch, int n_cu, hipStream_t st);
 hipError_t faqcs_launch_bgzf_index_chain(const uint8_t *comp, unsigned long long n_comp, int final, uint32_t *member_offset, uint32_t capacity, faqcs_bgzf_index_info *info,
@@ -143,7 +146,8 @@ struct PackStage {
 };
 
 // What faqcs_gunzip_device keeps on a context: the records of the pieces, the chain and the slices; one record for a forced start; the 16-bit
-// symbols (2 bytes per text byte); the events around a pass and the three stage times of the last call (faqcs_gunzip_time_ms).
+// symbols (2 bytes per text byte, and 64 KiB in front of them for the carried window of faqcs_gunzip_stream_device); the events around a
+// pass and the three stage times of the last call of either kind (faqcs_gunzip_time_ms).
 struct GunzipStage {
     DevBuf<uint4> rec, one, sym;
     hipEvent_t ev[2] = {nullptr, nullptr};

@@ -17,6 +17,10 @@
 //   decode    gz_run again (WRITE = true) per chain piece, into 16-bit symbols at the piece's position: a byte, or 0x8000 | k = byte k of the
 //             32 768 in front of this piece.  resolve_piece, over the chain in order, turns the markers of each piece's last 32 768 symbols
 //             into bytes (so the window of the next piece is bytes); narrow_slice makes text of everything and a CRC per slice.
+//   chunks    faqcs_gunzip_stream_*: gunzip_run with a carried State.  The walk begins where the state says (in mid-stream: a forced start), the
+//             symbols get a front of 32 768 that holds the carried window as bytes, so the first piece's markers resolve like any other's, and
+//             with final = 0 the walk stops at the last block boundary that is resident; the CRC so far and this call's share are folded as
+//             zlib's crc32_combine folds them.
 // A Sink here is faqcs_inflate.h's with 16-bit output and one more member: umin(v), the smallest v of the cooperating lanes.
 #pragma once
 #include "faqcs_inflate.h"
@@ -338,10 +342,11 @@ INF_HD uint32_t resolve_piece(uint16_t *sym, const ChainPiece &c, uint32_t lane,
     return bad;
 }
 
-// text[s.begin .. s.begin + s.n) from the symbols, four to a store; a marker is looked up in the piece's resolved window.
-// 1: a marker points in front of the member's first byte.
-INF_HD uint32_t narrow_slice(const uint16_t *sym, uint8_t *text, const Slice &s, const ChainPiece &c, uint32_t lane, uint32_t lanes)
+// text[s.begin - front .. s.begin - front + s.n) from the symbols, four to a store; a marker is looked up in the piece's resolved window.
+// front: the symbols in front of the call's text (0, or WIN: the carried window).  1: a marker points in front of the member's first byte.
+INF_HD uint32_t narrow_slice(const uint16_t *sym, uint8_t *text, const Slice &s, const ChainPiece &c, uint32_t front, uint32_t lane, uint32_t lanes)
 {
+    text += s.begin - front;
     uint32_t bad = 0;
     for (uint32_t i = 4 * lane; i < s.n; i += 4 * lanes) {
         const uint32_t m = s.n - i < 4 ? s.n - i : 4;
@@ -354,8 +359,8 @@ INF_HD uint32_t narrow_slice(const uint16_t *sym, uint8_t *text, const Slice &s,
             }
             w |= (v & 255u) << (8 * j);
         }
-        if (m == 4) memcpy(text + s.begin + i, &w, 4);
-        else for (uint32_t j = 0; j < m; ++j) text[s.begin + i + j] = (uint8_t)(w >> (8 * j));
+        if (m == 4) memcpy(text + i, &w, 4);
+        else for (uint32_t j = 0; j < m; ++j) text[i + j] = (uint8_t)(w >> (8 * j));
     }
     return bad;
 }
@@ -395,45 +400,77 @@ struct HostSymSink {
 
 // ---- the chain: host code of both forms -------------------------------------------------------------------------------------------------
 struct Info { uint64_t n_bytes, consumed; uint32_t n_members, overflow; int32_t error; uint32_t n_pieces, n_fixups, n_rounds; };
-struct MemberRec { uint64_t header_at, text_begin, len; uint32_t crc, isize; size_t chain_begin, chain_end; };
+// open: 0, or the phase in which the call leaves the member (final = 0); end_bit: where this call leaves it (open), behind its trailer (not)
+struct MemberRec { uint64_t header_at, text_begin, len; uint32_t crc, isize; size_t chain_begin, chain_end; uint32_t open; uint64_t end_bit; };
 struct MemberResult { uint32_t crc, bad; };
 enum { E_RECORD = -100 }; // gunzip_run: a pass returned a record that no run can produce
+
+// What faqcs_gunzip_stream_* carry from call to call (faqcs_gunzip_state of include/faqcs_mi.h without the window, which is the Backend's).
+enum { PH_BETWEEN = 0, PH_STREAM = 1, PH_TRAILER = 2 };
+struct State { uint64_t member_bytes, total_bytes, total_comp; uint32_t phase, bit, crc, window_bytes, members, reserved; };
 
 // A Backend is where the compressed bytes and the passes are: the host (HostBackend) or a device (faqcs_capi_seam.hip).
 //   int fetch(p, n, dst)                          comp[p .. p + n) -> dst (host memory)
 //   int count_grid(grid, n_grid)                  count_piece of every grid piece (start_bit = NO_BIT, grid = its index)
 //   int count_forced(pc)                          count_piece of one piece with a given start
-//   int write(chain, members, total, results)     decode, resolve, narrow: the text, and per member its CRC-32 and whether a marker left it
+//   int write(chain, members, front, window_bytes, total, results)
+//                                                 the carried window into the symbols' front (window_bytes of it), decode, resolve, narrow: the
+//                                                 text, and per member its CRC-32 and whether a marker left it
+//   int window_save(take_old, take_new, text_end) the caller's window, right-aligned: the last take_old symbols of the front, then
+//                                                 text[text_end - take_new .. text_end)
 // Each returns 0 or a FAQCS_E_* code, which ends the call.
+//
+// carry == nullptr: faqcs_gunzip_device / _host -- whole members, no front.  Else faqcs_gunzip_stream_*: the walk begins where *carry says,
+// the symbols have a front of WIN for the carried window (every position moves up by it; the continued member's member_pos is
+// WIN - window_bytes, so a marker of its first piece resolves into the front and marker_source, resolve_piece and narrow_slice have no
+// case for it), and with final = false the walk stops at the last block boundary that is resident instead of stating E_TRUNCATED: a forced
+// run that the input's end cut short is taken as far as its last whole block.  *carry is rewritten only when nothing overflows, and then
+// stands behind what info.n_bytes and info.consumed say.
 template <class Backend>
-int gunzip_run(Backend &B, uint64_t n_comp, uint32_t piece_bytes, uint32_t max_rounds, uint64_t capacity, Info &info)
+int gunzip_run(Backend &B, uint64_t n_comp, uint32_t piece_bytes, uint32_t max_rounds, uint64_t capacity, Info &info, State *carry = nullptr, bool final = true)
 {
     const uint32_t P = piece_bytes ? piece_bytes : DEFAULT_PIECE, R = max_rounds ? max_rounds : DEFAULT_ROUNDS;
     const uint32_t G = (uint32_t)((n_comp + P - 1) / P);
+    const State st0 = carry ? *carry : State{0, 0, 0, PH_BETWEEN, 0, 0, 0, 0, 0};
+    const uint32_t F = carry ? WIN : 0u;
     info = Info{0, 0, 0, 0, 0, 0, 0, 0};
     std::vector<Piece> grid;
     std::vector<ChainPiece> chain;
     std::vector<MemberRec> members;
     std::vector<uint8_t> win;
     uint64_t p = 0, total = 0;
-    for (;;) {
-        uint32_t hlen = 0;
-        int h = H_PARTIAL;
-        for (uint64_t have = 512;; have *= 8) { // the header: a window of what follows p, widened while the header is longer
-            const uint64_t avail = n_comp - p, take = have < avail ? have : avail;
-            if (!take) break;
-            win.resize(take);
-            if (int rc = B.fetch(p, (uint32_t)take, win.data())) return rc;
-            h = gz_header(win.data(), take, take == avail, hlen);
-            if (h != H_MORE) break;
+    bool walk = true;
+    if (st0.phase == PH_TRAILER) { // the open member's trailer first: it completes a member that has no text in this call
+        if (n_comp < 8) { if (final) info.error = (int32_t)inf::ST_E_TRUNCATED; walk = false; }
+        else {
+            uint8_t tr[8];
+            if (int rc = B.fetch(0, 8, tr)) return rc;
+            members.push_back(MemberRec{0, 0, 0, inf::le32(tr), inf::le32(tr + 4), 0, 0, 0, 64});
+            p = 8;
         }
-        if (p == n_comp || h == H_END) { info.consumed = h == H_END && p < n_comp ? n_comp : p; break; }
-        if (h != H_OK) { info.error = h == H_HEADER ? (int32_t)inf::ST_E_HEADER : (int32_t)inf::ST_E_TRUNCATED; info.consumed = p; break; }
-        MemberRec m{p, total, 0, 0, 0, chain.size(), 0};
-        uint64_t cur = 8 * (p + hlen), next = 0;
+    }
+    for (bool cont = st0.phase == PH_STREAM; walk; cont = false) {
+        MemberRec m{p, total, 0, 0, 0, chain.size(), 0, 0, 0};
+        uint64_t cur = st0.bit, next = 0;
+        if (!cont) {
+            uint32_t hlen = 0;
+            int h = H_PARTIAL;
+            for (uint64_t have = 512;; have *= 8) { // the header: a window of what follows p, widened while the header is longer
+                const uint64_t avail = n_comp - p, take = have < avail ? have : avail;
+                if (!take) break;
+                win.resize(take);
+                if (int rc = B.fetch(p, (uint32_t)take, win.data())) return rc;
+                h = gz_header(win.data(), take, take == avail, hlen);
+                if (h != H_MORE) break;
+            }
+            if (p == n_comp || h == H_END) { info.consumed = h == H_END && p < n_comp ? n_comp : p; break; }
+            if (h == H_PARTIAL && !final) { info.consumed = p; break; } // the rest of the header comes with the next call
+            if (h != H_OK) { info.error = h == H_HEADER ? (int32_t)inf::ST_E_HEADER : (int32_t)inf::ST_E_TRUNCATED; info.consumed = p; break; }
+            cur = 8 * (p + hlen);
+        }
         uint32_t rounds = 0, err = 0;
         for (bool first = true;; first = false) {
-            if ((cur >> 3) >= n_comp) { err = inf::ST_E_TRUNCATED; break; }
+            if ((cur >> 3) >= n_comp) { if (final) err = inf::ST_E_TRUNCATED; else m.open = PH_STREAM; break; }
             const uint32_t g = (uint32_t)((cur >> 3) / P);
             Piece pc{cur, 0, 0, g, 0};
             if (!grid.empty() && grid[g].start_bit == cur) pc = grid[g];
@@ -448,39 +485,75 @@ int gunzip_run(Backend &B, uint64_t n_comp, uint32_t piece_bytes, uint32_t max_r
                 }
                 if (int rc = B.count_forced(pc)) return rc;
             }
-            if (pc.state & 255u) { err = pc.state & 255u; break; }
+            const bool cut = !final && (pc.state & 255u) == inf::ST_E_TRUNCATED; // the input's end, not the data: the last whole block counts
+            if (cut && pc.end_bit <= cur) { m.open = PH_STREAM; break; }
+            if ((pc.state & 255u) && !cut) { err = pc.state & 255u; break; }
             if (pc.end_bit <= cur || pc.end_bit > 8 * n_comp) return E_RECORD; // (a record that cannot be: never follow it)
-            chain.push_back(ChainPiece{pc.start_bit, pc.end_bit, (uint32_t)(total + m.len), (uint32_t)pc.n_out, (uint32_t)total, 0}); // (32 bits: used when nothing overflows)
+            // (32 bits: used when nothing overflows)
+            chain.push_back(ChainPiece{pc.start_bit, pc.end_bit, (uint32_t)(F + total + m.len), (uint32_t)pc.n_out, cont ? F - st0.window_bytes : (uint32_t)(F + total), 0});
             m.len += pc.n_out;
+            cur = pc.end_bit;
+            if (cut) { m.open = PH_STREAM; break; }
             if (pc.state >> 8) { // the final block: the trailer in the next whole byte
                 const uint64_t t = (pc.end_bit + 7) >> 3;
-                if (t + 8 > n_comp) { err = inf::ST_E_TRUNCATED; break; }
+                if (t + 8 > n_comp) {
+                    if (final) err = inf::ST_E_TRUNCATED; else { m.open = PH_TRAILER; cur = 8 * t; }
+                    break;
+                }
                 uint8_t tr[8];
                 if (int rc = B.fetch(t, 8, tr)) return rc;
                 m.crc = inf::le32(tr); m.isize = inf::le32(tr + 4);
                 next = t + 8;
                 break;
             }
-            cur = pc.end_bit;
         }
         if (err) { chain.resize(m.chain_begin); info.error = (int32_t)err; info.consumed = p; break; }
         m.chain_end = chain.size();
+        m.end_bit = m.open ? cur : 8 * next;
         total += m.len;
         members.push_back(m);
+        if (m.open) { info.consumed = cur >> 3; break; }
         p = next;
     }
-    info.n_bytes = total; info.n_members = (uint32_t)members.size(); info.n_pieces = (uint32_t)chain.size();
-    info.overflow = (total > capacity || total >= (1ull << 32)) ? 1u : 0u;
-    if (info.overflow || members.empty()) return 0;
+    const bool open_last = !members.empty() && members.back().open;
+    info.n_bytes = total; info.n_members = (uint32_t)members.size() - (open_last ? 1u : 0u); info.n_pieces = (uint32_t)chain.size();
+    info.overflow = (total > capacity || total >= (1ull << 32) - F) ? 1u : 0u;
+    if (info.overflow || (members.empty() && !carry)) return 0;
     for (const MemberRec &m : members)
-        for (size_t k = m.chain_begin; k < m.chain_end; ++k) chain[k].member_end = (uint32_t)(m.text_begin + m.len);
-    std::vector<MemberResult> res(members.size());
-    if (int rc = B.write(chain, members, (uint32_t)total, res)) return rc;
+        for (size_t k = m.chain_begin; k < m.chain_end; ++k) chain[k].member_end = (uint32_t)(F + m.text_begin + m.len);
+    std::vector<MemberResult> res(members.size(), MemberResult{0, 0});
+    if (!chain.empty())
+        if (int rc = B.write(chain, members, F, st0.phase == PH_STREAM ? st0.window_bytes : 0u, (uint32_t)total, res)) return rc;
+    Pow pw;
+    pow_init(pw);
+    size_t n_good = members.size();
     for (size_t k = 0; k < members.size(); ++k) { // CRC and length are looked at last
         const MemberRec &m = members[k];
-        const int32_t st = res[k].bad ? (int32_t)inf::ST_E_DATA : (uint32_t)m.len != m.isize ? (int32_t)inf::ST_E_LENGTH : res[k].crc != m.crc ? (int32_t)inf::ST_E_CRC : 0;
-        if (st) { info.error = st; info.n_members = (uint32_t)k; info.n_bytes = m.text_begin; info.consumed = m.header_at; break; }
+        const bool carried = k == 0 && st0.phase != PH_BETWEEN;
+        // what zlib's crc32_combine makes of the CRC the calls in front carried and this call's share
+        if (carried) res[k].crc ^= inf::multmodp(x8n_modp(pw, m.len), st0.crc);
+        const uint64_t len = (carried ? st0.member_bytes : 0) + m.len;
+        const int32_t st = res[k].bad ? (int32_t)inf::ST_E_DATA : m.open ? 0 : (uint32_t)len != m.isize ? (int32_t)inf::ST_E_LENGTH : res[k].crc != m.crc ? (int32_t)inf::ST_E_CRC : 0;
+        if (st) { info.error = st; info.n_members = (uint32_t)k; info.n_bytes = m.text_begin; info.consumed = m.header_at; n_good = k; break; }
     }
+    if (!carry) return 0;
+    State &s = *carry;
+    for (size_t k = 0; k < n_good; ++k) {
+        const MemberRec &m = members[k];
+        const bool carried = k == 0 && st0.phase != PH_BETWEEN;
+        if (!m.open) { ++s.members; s.member_bytes = 0; s.crc = 0; s.window_bytes = 0; s.phase = PH_BETWEEN; s.bit = 0; continue; }
+        s.member_bytes = (carried ? st0.member_bytes : 0) + m.len;
+        s.crc = res[k].crc;
+        s.window_bytes = s.member_bytes < WIN ? (uint32_t)s.member_bytes : WIN;
+        s.phase = m.open;
+        s.bit = m.open == PH_STREAM ? (uint32_t)(m.end_bit & 7u) : 0u;
+        if (m.len) { // (no text of it in this call: the window stands as it is)
+            const uint32_t take_new = m.len < WIN ? (uint32_t)m.len : WIN;
+            if (int rc = B.window_save(s.window_bytes - take_new, take_new, (uint32_t)(m.text_begin + m.len))) return rc; // (old ones: at most window_bytes of entry)
+        }
+    }
+    s.total_bytes += info.n_bytes;
+    s.total_comp += info.consumed;
     return 0;
 }
 
@@ -509,6 +582,8 @@ struct HostBackend {
     const uint8_t *comp;
     uint32_t n_comp, piece_bytes;
     std::vector<uint8_t> text;
+    std::vector<uint16_t> sym;
+    uint8_t *window = nullptr; // faqcs_gunzip_stream_host: the caller's WIN bytes
     inf::Tables T;
     HostBackend(const uint8_t *c, uint64_t n, uint32_t pb) : comp(c), n_comp((uint32_t)n), piece_bytes(pb ? pb : DEFAULT_PIECE) { HostSymSink S{nullptr}; inf::crc_init(T, S); }
     int fetch(uint64_t p, uint32_t n, uint8_t *dst) { memcpy(dst, comp + p, n); return 0; }
@@ -519,9 +594,11 @@ struct HostBackend {
         return 0;
     }
     int count_forced(Piece &pc) { HostSymSink S{nullptr}; count_piece(comp, n_comp, piece_bytes, pc, T, S); return 0; }
-    int write(const std::vector<ChainPiece> &chain, const std::vector<MemberRec> &members, uint32_t total, std::vector<MemberResult> &res)
+    int write(const std::vector<ChainPiece> &chain, const std::vector<MemberRec> &members, uint32_t front, uint32_t window_bytes, uint32_t total,
+              std::vector<MemberResult> &res)
     {
-        std::vector<uint16_t> sym((size_t)total); // (exactly: a write beyond is the sanitizers')
+        sym.assign((size_t)front + total, 0); // (exactly: a write beyond is the sanitizers')
+        for (uint32_t i = WIN - window_bytes; i < WIN && window_bytes; ++i) sym[i] = window[i];
         std::vector<uint32_t> dst(chain.size()), rbad(chain.size());
         text.assign((size_t)total, 0);
         for (size_t k = 0; k < chain.size(); ++k) { HostSymSink S{sym.data() + chain[k].pos}; dst[k] = decode_piece(comp, n_comp, chain[k], T, S); }
@@ -534,12 +611,19 @@ struct HostBackend {
         for (size_t s = 0; s < slices.size(); ++s) {
             const Slice &sl = slices[s];
             const ChainPiece &c = chain[sl.piece];
-            sres[s].bad = narrow_slice(sym.data(), text.data(), sl, c, 0, 1);
+            sres[s].bad = narrow_slice(sym.data(), text.data(), sl, c, front, 0, 1);
             uint32_t crc = 0;
-            for (uint32_t l = 0; l < inf::CRC_LANES; ++l) crc ^= inf::crc_slice(T, text.data() + sl.begin, sl.n, l);
+            for (uint32_t l = 0; l < inf::CRC_LANES; ++l) crc ^= inf::crc_slice(T, text.data() + (sl.begin - front), sl.n, l);
             sres[s].crc = inf::multmodp(x8n_modp(pw, (uint64_t)c.member_end - (sl.begin + sl.n)), crc);
         }
         fold_results(chain, members, slices, sres.data(), dst.data(), rbad.data(), res);
+        return 0;
+    }
+    int window_save(uint32_t take_old, uint32_t take_new, uint32_t text_end)
+    {
+        uint8_t *w = window + (WIN - take_old - take_new);
+        for (uint32_t j = 0; j < take_old; ++j) w[j] = (uint8_t)sym[WIN - take_old + j]; // (the front, never `window`: w runs ahead of what it reads)
+        memcpy(w + take_old, text.data() + (text_end - take_new), take_new);
         return 0;
     }
 };

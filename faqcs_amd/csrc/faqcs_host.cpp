@@ -294,6 +294,47 @@ extern "C" int faqcs_gunzip_host(const uint8_t *comp, uint64_t n_comp, uint32_t 
     return 0;
 }
 
+int gunzip_state_check_args(const char *who, const faqcs_gunzip_state *s)
+{
+    const std::string w(who);
+    if (!s || !s->window) return fail(FAQCS_E_INVAL, w + ": null state or window");
+    if (s->phase > FAQCS_GUNZIP_TRAILER) return fail(FAQCS_E_INVAL, w + ": the phase is BETWEEN, STREAM or TRAILER");
+    if (s->bit > 7 || (s->bit && s->phase != FAQCS_GUNZIP_STREAM)) return fail(FAQCS_E_INVAL, w + ": bit is 0 .. 7, and 0 outside the phase STREAM");
+    if (s->window_bytes != (s->member_bytes < faqcs_gunzip::WIN ? s->member_bytes : faqcs_gunzip::WIN)) return fail(FAQCS_E_INVAL, w + ": window_bytes is min(member_bytes, 32 768)");
+    if (s->reserved) return fail(FAQCS_E_INVAL, w + ": reserved is 0");
+    return 0;
+}
+
+void gunzip_state_in(const faqcs_gunzip_state *s, faqcs_gunzip::State *o)
+{
+    *o = faqcs_gunzip::State{s->member_bytes, s->total_bytes, s->total_comp, s->phase, s->bit, s->crc, s->window_bytes, s->members, 0};
+}
+
+void gunzip_state_out(const faqcs_gunzip::State &s, faqcs_gunzip_state *o)
+{
+    o->member_bytes = s.member_bytes; o->total_bytes = s.total_bytes; o->total_comp = s.total_comp; o->phase = s.phase; o->bit = s.bit;
+    o->crc = s.crc; o->window_bytes = s.window_bytes; o->members = s.members;
+}
+
+// The host statement of faqcs_gunzip_stream_device: the same walk with the carried state, the caller's window in host memory.
+extern "C" int faqcs_gunzip_stream_host(const uint8_t *comp, uint64_t n_comp, int final, uint32_t piece_bytes, uint32_t max_rounds, faqcs_gunzip_state *state,
+                                        const faqcs_gunzip_out *out)
+{
+    if (int rc = gunzip_check_args("faqcs_gunzip_stream_host", comp, n_comp, piece_bytes, out)) return rc;
+    if (int rc = gunzip_state_check_args("faqcs_gunzip_stream_host", state)) return rc;
+    std::unique_ptr<faqcs_gunzip::HostBackend> B(new faqcs_gunzip::HostBackend(comp, n_comp, piece_bytes));
+    B->window = state->window;
+    faqcs_gunzip::Info info;
+    faqcs_gunzip::State st;
+    gunzip_state_in(state, &st);
+    if (int rc = faqcs_gunzip::gunzip_run(*B, n_comp, piece_bytes, max_rounds, out->capacity_bytes, info, &st, final != 0))
+        return rc == faqcs_gunzip::E_RECORD ? fail(FAQCS_E_INVAL, "faqcs_gunzip_stream_host: a piece record that no run produces") : rc;
+    if (!info.overflow && info.n_bytes) memcpy(out->text, B->text.data(), info.n_bytes);
+    gunzip_info_out(info, out->info);
+    gunzip_state_out(st, state);
+    return 0;
+}
+
 int deflate_check_args(const char *who, const uint8_t *text, uint64_t n_text, uint32_t member_bytes, int final, int mode, const faqcs_deflate_out *out)
 {
     const std::string w(who);

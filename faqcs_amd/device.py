@@ -303,6 +303,50 @@ def gunzipped_text(engine, comp, capacity=None, piece_bytes=0, max_rounds=0):
     return o_text[a:a + int(p.n_bytes)]
 
 
+class GunzipStream:
+    """One ordinary gzip file fed to the device in chunks (faqcs_gunzip_stream_device).  It owns what goes from call to call: the state
+    (host memory) and the 32 KiB window (device memory).  Two files are two GunzipStreams on one engine, fed in any order."""
+
+    def __init__(self, engine, device=None, piece_bytes=0, max_rounds=0):
+        import torch
+
+        self.engine, self.piece_bytes, self.max_rounds = engine, piece_bytes, max_rounds
+        self.window = torch.zeros(capi.GUNZIP_WINDOW, dtype=torch.uint8, device=device if device is not None else "cuda")
+        self.state = capi.GunzipState()
+        self.state.window = self.window.data_ptr()
+
+    def feed(self, comp, final, capacity=None):
+        """comp: uint8 CUDA tensor, the file from where the previous feed's info.consumed left it (any alignment); final: these are its
+        last bytes.  capacity: bytes of text to make room for (default: four times the compressed bytes; the call is repeated once with
+        what info asks for when that is too little -- an overflow leaves the state alone).  Returns (text, info): the text this call
+        delivered, uint8 [n_bytes], a view laid out as gunzipped_text()'s, and the capi.GunzipInfo.  info.consumed == 0 with no text:
+        the chunk holds no whole block, feed a larger one.  A bad member does NOT raise: info.error is its code (see
+        engine.lib.faqcs_inflate_error_text; member self.state.members of the file), and text, info.consumed and the state are those of
+        the members in front of it within this call, which the caller still has to take -- the state says they were handed on."""
+        import torch
+
+        dev = comp.device
+        comp = comp.contiguous()
+        n_comp = int(comp.numel())
+        cap = 4 * n_comp + 4096 if capacity is None else int(capacity)
+        front = 64
+        info = torch.zeros(5, dtype=torch.int64, device=dev)
+        for attempt in range(2):
+            o_text = torch.empty(front + cap + capi.ARENA_PAD_AFTER + 16, dtype=torch.uint8, device=dev)
+            shift = (-(o_text.data_ptr() + front)) % 16
+            out = capi.GunzipOut(o_text.data_ptr() + front + shift, cap, info.data_ptr())
+            torch.cuda.current_stream(dev).synchronize()  # the library's compute stream is its own: the input must be complete
+            self.engine.gunzip_stream_device(comp.data_ptr() if n_comp else None, n_comp, final, self.state, out, self.piece_bytes, self.max_rounds)
+            p = capi.GunzipInfo.from_buffer_copy(info.cpu().numpy().tobytes())
+            if not p.overflow:
+                break
+            if attempt or p.n_bytes >= (1 << 32) - capi.GUNZIP_WINDOW:
+                raise FaqcsError(capi.E_INVAL, "faqcs_gunzip_stream_device: the text needs %d bytes, the output holds %d; feed a shorter chunk" % (p.n_bytes, cap))
+            cap = int(p.n_bytes)
+        a = front + shift
+        return o_text[a:a + int(p.n_bytes)], p
+
+
 def deflated_bgzf(engine, text, member_bytes=0, final=True, capacity=None, mode=capi.DEFLATE_FAST):
     """`text` as BGZF members, compressed on the device (faqcs_deflate_device_mode).
 

@@ -59,6 +59,36 @@ def gunzip_host(comp, piece_bytes=0, max_rounds=0, capacity=None, lib=None):
     return (b"" if info.overflow else store[shift:shift + info.n_bytes].tobytes()), d
 
 
+def gunzip_state(window):
+    """A zeroed capi.GunzipState over `window`, the address of the caller's capi.GUNZIP_WINDOW bytes: what a file's first call takes."""
+    st = capi.GunzipState()
+    st.window = window
+    return st
+
+
+def gunzip_stream_host(comp, final, state, window, piece_bytes=0, max_rounds=0, capacity=None, lib=None):
+    """faqcs_gunzip_stream_host (host only, no GPU): one chunk of an ordinary gzip file -- `comp` (bytes or a uint8 array) is the file from
+    where the previous call's info["consumed"] left it, final says that these are its last bytes.  state: the file's capi.GunzipState
+    (gunzip_state() before the first call), rewritten in place; window: the uint8 array of capi.GUNZIP_WINDOW bytes it points to (kept
+    alive by the caller).  capacity: bytes of text to make room for (default: found with a first call, which leaves the state alone).
+    Returns (text bytes of this call, info dict) -- what faqcs_gunzip_stream_device states for the same bytes, field for field."""
+    lib = lib or capi.load_library()
+    buf = np.frombuffer(comp, dtype=np.uint8) if isinstance(comp, (bytes, bytearray, memoryview)) else np.ascontiguousarray(comp, dtype=np.uint8)
+    assert state.window == window.ctypes.data and window.nbytes >= capi.GUNZIP_WINDOW
+    info = capi.GunzipInfo()
+    for cap in ([0, None] if capacity is None else [int(capacity)]):
+        cap = int(info.n_bytes) if cap is None else cap
+        store = np.zeros(cap + 32, dtype=np.uint8)
+        shift = (-store.ctypes.data) % 16
+        out = capi.GunzipOut(store.ctypes.data + shift, cap, C.addressof(info))
+        _check(lib, lib.faqcs_gunzip_stream_host(buf.ctypes.data if len(buf) else None, len(buf), 1 if final else 0, int(piece_bytes), int(max_rounds),
+                                                 C.byref(state), C.byref(out)))
+        if not info.overflow:
+            break
+    d = {f: int(getattr(info, f)) for f, _ in capi.GunzipInfo._fields_}
+    return (b"" if info.overflow else store[shift:shift + info.n_bytes].tobytes()), d
+
+
 def deflate_host(text, member_bytes=0, final=True, lib=None, mode=capi.DEFLATE_FAST):
     """faqcs_deflate_host_mode (host only, no GPU; mode: capi.DEFLATE_FAST, what faqcs_deflate_host does, or capi.DEFLATE_DENSE): `text` (bytes or a uint8 array) as BGZF members of member_bytes bytes of text each (0: 65 280),
     the EOF member behind them when final.  Returns (comp bytes, member_offset uint32 [n_members + 1], n_stored): the bytes
@@ -233,8 +263,15 @@ class HipEngine:
         when it returns."""
         _check(self.lib, self.lib.faqcs_gunzip_device(self.ctx, d_comp, int(n_comp), int(piece_bytes), int(max_rounds), C.byref(out)))
 
+    def gunzip_stream_device(self, d_comp, n_comp, final, state, out, piece_bytes=0, max_rounds=0):
+        """faqcs_gunzip_stream_device: one chunk of an ordinary gzip file in device memory (d_comp: the file from where the previous call's
+        consumed left it) -> this call's text in the arrays of `out`; state: the file's capi.GunzipState in host memory, its window in
+        device memory.  The call BLOCKS, as gunzip_device() does."""
+        _check(self.lib, self.lib.faqcs_gunzip_stream_device(self.ctx, d_comp, int(n_comp), 1 if final else 0, int(piece_bytes), int(max_rounds),
+                                                             C.byref(state), C.byref(out)))
+
     def gunzip_time_ms(self):
-        """(count ms, decode ms, resolve ms) of the last gunzip_device() on this engine (HIP events on the compute stream)."""
+        """(count ms, decode ms, resolve ms) of the last gunzip_device() or gunzip_stream_device() on this engine (HIP events on the compute stream)."""
         a, g, r = C.c_double(), C.c_double(), C.c_double()
         _check(self.lib, self.lib.faqcs_gunzip_time_ms(self.ctx, C.byref(a), C.byref(g), C.byref(r)))
         return a.value, g.value, r.value

@@ -533,7 +533,7 @@ int  faqcs_inflate_host(const uint8_t *comp, uint64_t n_comp, const uint32_t *me
  *                 as faqcs_inflate_device accepts them.  No alignment is asked of d_comp; nothing outside d_comp[0 .. n_comp) is read.
  *   end of data   bytes behind the last member that do not start 1f 8b end the data without an error (consumed = n_comp), as for gzread and
  *                 faqcs_bgzf_index_host.  A last member whose header, stream or trailer is incomplete is E_TRUNCATED with consumed at its
- *                 header: there is no final = 0 in this version, a member must be resident whole.
+ *                 header: a member must be resident whole here (faqcs_gunzip_stream_device, below, takes chunks).
  *   errors        per member and sequential, as in faqcs_inflate_device: the first bad member in input order decides, n_members is its index,
  *                 consumed where its header starts, n_bytes the text of the members in front of it, and that text is delivered byte-exact
  *                 (what lies behind it in `text` is unspecified).  E_DATA: an invalid code or code set, block type 3, LEN != ~NLEN, a
@@ -576,6 +576,63 @@ typedef struct faqcs_gunzip_out {
 } faqcs_gunzip_out;
 int  faqcs_gunzip_device(faqcs_ctx *ctx, const uint8_t *d_comp, uint64_t n_comp, uint32_t piece_bytes, uint32_t max_rounds, const faqcs_gunzip_out *out);
 int  faqcs_gunzip_host(const uint8_t *comp, uint64_t n_comp, uint32_t piece_bytes, uint32_t max_rounds, const faqcs_gunzip_out *out);
+
+/* The same inflate in chunks the caller chooses: a member need not be resident whole, and it may hold 4 GiB of text or more.  A chunk may end
+ * anywhere -- inside a deflate block, a header or a trailer.  What goes from one call to the next is the caller's, per file: two files may
+ * be fed alternately on one context.  Everything faqcs_gunzip_device states holds here unless said otherwise.
+ *   input         comp[0 .. n_comp) is the file from where the previous call's `consumed` left it: the caller presents comp[consumed ..)
+ *                 again with more bytes behind it.  final = 1: these are the file's last bytes.
+ *   output        info->n_bytes is the text THIS call delivered, the open member's share included; consumed the bytes of this call's input
+ *                 that are done with; n_members the members completed in this call; n_pieces, n_fixups and n_rounds are this call's.
+ *   final = 0     the call delivers every whole deflate block that is resident and stops at the last block boundary:
+ *                   in mid-stream          phase STREAM, consumed = boundary_bit >> 3, bit = boundary_bit & 7
+ *                   a header cut short     phase BETWEEN, consumed at its first byte
+ *                   a final block without its 8 trailer bytes
+ *                                          phase TRAILER, consumed at the first trailer byte
+ *                 consumed == 0 with an unchanged state: the chunk holds no whole block behind the carried position -- make it larger, as
+ *                 for faqcs_parse_device.  Whether bytes behind a member are another member or the data's end is judged from the bytes at
+ *                 that position alone, in the call that reaches them.
+ *   final = 1     what is incomplete is E_TRUNCATED.  With a zeroed state this is faqcs_gunzip_device / _host exactly: the same text, the
+ *                 same info field for field.
+ *   the state     HOST memory in both forms, all zero (but `window`) before a file's first call.  After every call crc is the CRC-32 (as
+ *                 zlib's crc32() states it) of the open member's text so far, window[32768 - window_bytes .. 32768) that text's last bytes,
+ *                 member_bytes, members, total_bytes and total_comp the sums.  For any sequence of chunk ends the concatenated text is what
+ *                 the single call, and gzread, deliver.
+ *   errors        per member and sequential.  Nothing of the bad member is delivered BY THIS CALL: n_bytes and n_members are those of the
+ *                 members in front of it within this call, consumed is at its header -- or 0 when it is the member that was open at entry,
+ *                 and then the state is unchanged; else the state stands behind what n_bytes and consumed say.  E_LENGTH and E_CRC of a
+ *                 member that began in an earlier call are reported when its trailer is read: earlier calls have handed its text on, as for
+ *                 any gzread caller.  E_LENGTH compares member_bytes modulo 2^32 with ISIZE.  E_SERIAL counts max_rounds within one
+ *                 member and one call.
+ *   capacity      as above, with total >= 2^32 - 32 768 as the limit: overflow = 1, nothing but info is written, the state is untouched.
+ *                 The remedies are a larger text buffer or a SHORTER n_comp: any prefix is a valid chunk.
+ *   the scheme    the continued position is a forced start, like a member's first block; the grid of pieces lies over this call's bytes.
+ *                 The symbols have a front of 32 768 that holds the carried window, so a marker of the first piece resolves into it
+ *                 (DESIGN.md section 4.8a).  Scratch is 64 KiB more than the single call's.
+ *   n_comp == 0   with final = 0: zeros, the state as it is; with final = 1 in phase STREAM or TRAILER: E_TRUNCATED.
+ *   THE CALL BLOCKS, as the single call does; faqcs_gunzip_time_ms reports the last gunzip call of either kind.
+ *   FAQCS_E_INVAL: everything the single call refuses; a null state or state->window; phase > 2; bit > 7, or bit != 0 outside STREAM;
+ *   window_bytes != min(member_bytes, 32 768); reserved != 0. */
+enum { FAQCS_GUNZIP_BETWEEN = 0,   /* the next byte is a member header, or the end of the data */
+       FAQCS_GUNZIP_STREAM  = 1,   /* the next bit continues the open member's deflate stream at a block boundary */
+       FAQCS_GUNZIP_TRAILER = 2 }; /* the open member's final block is done; its 8 trailer bytes come next */
+typedef struct faqcs_gunzip_state {          /* HOST memory in both forms; all zero except `window` before a file's first call */
+    uint64_t member_bytes;   /* text of the open member that the calls so far delivered */
+    uint64_t total_bytes;    /* text delivered over all calls */
+    uint64_t total_comp;     /* compressed bytes consumed over all calls */
+    uint32_t phase;
+    uint32_t bit;            /* STREAM: the stream goes on at bit `bit` (0..7, LSB first) of the next call's comp[0]; else 0 */
+    uint32_t crc;            /* CRC-32, as zlib's crc32() states it, of those member_bytes bytes */
+    uint32_t window_bytes;   /* min(member_bytes, 32768) */
+    uint32_t members;        /* members completed so far */
+    uint32_t reserved;       /* 0 */
+    uint8_t *window;         /* 32 768 bytes, the caller's: DEVICE memory for _device, host memory for _host;
+                                valid: window[32768 - window_bytes .. 32768), the open member's last text bytes */
+} faqcs_gunzip_state;
+int  faqcs_gunzip_stream_device(faqcs_ctx *ctx, const uint8_t *d_comp, uint64_t n_comp, int final, uint32_t piece_bytes, uint32_t max_rounds,
+                                faqcs_gunzip_state *state, const faqcs_gunzip_out *out);
+int  faqcs_gunzip_stream_host(const uint8_t *comp, uint64_t n_comp, int final, uint32_t piece_bytes, uint32_t max_rounds,
+                              faqcs_gunzip_state *state, const faqcs_gunzip_out *out);
 
 /* The step behind the device seam: compressed output.  Text in device memory (what faqcs_render_device() assembled, or any bytes) -> BGZF
  * members in device memory, so that a third of the bytes leave the card and the result is what faqcs_inflate_device() takes.
@@ -843,8 +900,8 @@ int  faqcs_pair_time_ms(faqcs_ctx *ctx, double *check_ms, double *finish_ms);
 int  faqcs_render_pair_time_ms(faqcs_ctx *ctx, double *scan_ms, double *gather_ms);
 /* the same for the LAST faqcs_inflate_device() on the context: the scan of the headers (scan_ms), the decode with its CRC and the status (decode_ms) */
 int  faqcs_inflate_time_ms(faqcs_ctx *ctx, double *scan_ms, double *decode_ms);
-/* the same for the LAST faqcs_gunzip_device() on the context: every count round (count_ms), the decode pass and the narrowing with its CRC
- * (decode_ms), the resolve pass -- the serial part, one step per piece -- (resolve_ms) */
+/* the same for the LAST faqcs_gunzip_device() or faqcs_gunzip_stream_device() on the context: every count round (count_ms), the decode pass,
+ * the narrowing with its CRC and the two window kernels (decode_ms), the resolve pass -- the serial part, one step per piece -- (resolve_ms) */
 int  faqcs_gunzip_time_ms(faqcs_ctx *ctx, double *count_ms, double *decode_ms, double *resolve_ms);
 /* the same for the LAST faqcs_deflate_device() on the context: the members' encoding into their slots (encode_ms), sizes, positions and the gather (gather_ms) */
 int  faqcs_deflate_time_ms(faqcs_ctx *ctx, double *encode_ms, double *gather_ms);

@@ -3,7 +3,10 @@ and 256 KiB, against, in the same process: (a) ONE zlib thread (zlib.decompresso
 same text as BGZF members of 65 280 bytes -- what the second pass and the probe cost --; (c) a torch device-to-device copy of the text.
 Prints one JSON line; --out FILE also writes it there.
 
-    python tools/gunzip_bench.py [--mib 256] [--distinct-mib 64] [--reps 7] [--out profiles/inflate/gunzip_bench.json]
+    python tools/gunzip_bench.py [--mib 256] [--distinct-mib 64] [--reps 7] [--chunks 4,16] [--out profiles/inflate/gunzip_bench.json]
+
+--chunks N[,N..] also feeds the same input as N equal chunks through device.GunzipStream (faqcs_gunzip_stream_device) at the first piece
+size and reports the total wall time, its ratio to the single call of the same run, and the rounds of every call.
 
 The text is inflate_bench.shaped_text; --distinct-mib of it are one gzip member, and the file holds that member --mib / --distinct-mib
 times (`cat` of equal files).  The three stage times are the library's (HIP events around every pass: faqcs_gunzip_time_ms), `call_ms` is
@@ -36,6 +39,33 @@ def zlib_thread_ms(member):
     return (time.perf_counter() - t0) * 1e3, n
 
 
+def streamed(eng, d_comp, n_chunks, piece_bytes, reps, n_text, n_members, single_ms):
+    """The same input as n_chunks equal chunks through device.GunzipStream (faqcs_gunzip_stream_device): every call gets the bytes from
+    the previous call's consumed to the next chunk end.  -> the total wall time (median of reps after a warm-up), its ratio to the single
+    call of the same build, and the rounds of every call of the last repetition"""
+    from faqcs_amd.device import GunzipStream
+
+    n_comp = int(d_comp.numel())
+    ends = [n_comp * (k + 1) // n_chunks for k in range(n_chunks)]
+    cap = int(1.5 * n_text / n_chunks) + (8 << 20)
+    wall, rounds = [], []
+    for rep in range(reps + 1):
+        gzs = GunzipStream(eng, piece_bytes=piece_bytes)
+        at, rounds, total = 0, [], 0.0
+        for k, end in enumerate(ends):
+            t0 = time.perf_counter()
+            text, info = gzs.feed(d_comp[at:end], k == n_chunks - 1, capacity=cap)
+            total += (time.perf_counter() - t0) * 1e3
+            assert info.error == 0, info.error
+            at += int(info.consumed)
+            rounds.append(int(info.n_rounds))
+            del text
+        assert (gzs.state.total_bytes, gzs.state.members, gzs.state.total_comp, gzs.state.phase) == (n_text, n_members, n_comp, 0), "the streamed run differs"
+        wall.append(total)
+    wm = float(np.median(wall[1:]))
+    return {"call_ms_total": round(wm, 3), "over_single_call": round(wm / single_ms, 3), "n_rounds_per_call": rounds, "text_GB_per_s": round(n_text / wm / 1e6, 2)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mib", type=int, default=256)
@@ -43,6 +73,7 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--levels", default="1,6")
     ap.add_argument("--pieces-kib", default="64,128,256")
+    ap.add_argument("--chunks", default="", help="N[,N..]: also feed the input as N equal chunks through GunzipStream, at the first piece size")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
@@ -85,6 +116,9 @@ def main():
             row["pieces"][str(kib)] = {"n_pieces": int(p.n_pieces), "n_fixups": int(p.n_fixups), "n_rounds": int(p.n_rounds), "count_ms": round(cm, 3),
                                        "decode_ms": round(dm, 3), "resolve_ms": round(rm, 3), "call_ms": round(wm, 3), "resolve_share": round(rm / wm, 3),
                                        "text_GB_per_s": round(n_text / wm / 1e6, 2)}
+        for n_chunks in [int(x) for x in a.chunks.split(",") if x]:
+            row.setdefault("chunks", {})[str(n_chunks)] = streamed(eng, store[1:1 + len(comp)], n_chunks, int(a.pieces_kib.split(",")[0]) << 10, a.reps, n_text, copies,
+                                                                  row["pieces"][a.pieces_kib.split(",")[0]]["call_ms"])
         copy = []
         for rep in range(a.reps + 1):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
