@@ -746,6 +746,19 @@ def grid_cases():
     return [c for c in catalogue() if c.kind == "grid"]
 
 
+def raw_stream(case):
+    """-> (the raw deflate stream of a Case, the eight trailer bytes its member states): catalogue() wraps every stream with ic.member()'s
+    plain BGZF header of 18 bytes"""
+    assert case.member[:4] == b"\x1f\x8b\x08\x04" and case.member[10:14] == b"\x06\x00BC"
+    return case.member[18:-8], case.member[-8:]
+
+
+def stored_prefix(data):
+    """a NON-final stored block of `data`, as bytes: it ends on a byte boundary, so stored_prefix(data) + raw is the stream `raw` with
+    one more block in front, every bit of `raw` where it was within its byte"""
+    return Stream().stored(data).getvalue()
+
+
 def coverage():
     """What the writer emitted in the VALID cases (every symbol of a valid stream is decoded):
        code_lengths       {"lit" / "dist" / "cl": the code lengths of emitted symbols}
