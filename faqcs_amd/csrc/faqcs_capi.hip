@@ -402,6 +402,7 @@ static int enqueue(faqcs_ctx *c, const uint8_t *d_seq, const uint8_t *d_qual, co
                    const uint32_t *host_off = nullptr)
 {
     const Submission s{d_seq, d_qual, d_tn, d_off, seg, host_off, n, max_len, n_seg, d_res};
+    if (int rc = check_kmers(c, s)) return rc;
     Timing *tm = nullptr;
     const bool adapters = s.n && c->prm.n_adapters;
     if (s.n) { if (int rc = take_timing(c, tm)) return rc; }

@@ -416,6 +416,20 @@ template <class F> static int for_each_epoch_run(const uint32_t *seg, uint32_t n
     return 0;
 }
 
+// What the k-mer tail of a submission refuses, asked BEFORE anything of the submission is enqueued: a refused submission leaves the context as
+// it was -- its reads are not trimmed into the counter block, and no timing event of it is left half recorded (faqcs_sync asks for the time
+// between k0 and k1: the error of an event that was never recorded stayed behind as HIP's last error and failed the NEXT submission's trim launch)
+int check_kmers(faqcs_ctx *c, const Submission &s)
+{
+    if (!c->partitioned || !c->kmer_active || s.n == 0) return 0;
+    if (c->seg_epoch.size() != s.n_seg) return fail(FAQCS_E_INVAL, "faqcs_submit: faqcs_kmer_set_epochs() must give one epoch per segment of the submission");
+    if (c->kg.direct) return 0;
+    size_t runs = 0;
+    (void)for_each_epoch_run(s.seg, s.n_seg, c->seg_epoch, [&](uint32_t, uint32_t) -> int { ++runs; return 0; });
+    if (runs > (size_t)KG_MAX_RUNS) return fail(FAQCS_E_INVAL, "faqcs_submit: more than 1000 runs of segments with one epoch in a submission");
+    return 0;
+}
+
 // owner-partitioned mode: this shard's runs of k-mers (super-k-mer items) grouped by owner rank; the caller exchanges them
 static int kmer_send_items(faqcs_ctx *c, Timing *tm, const Submission &s)
 {
@@ -549,7 +563,13 @@ static int kmer_rarefaction(faqcs_ctx *c, Timing *tm, const Submission &s)
 int enqueue_kmers(faqcs_ctx *c, Timing *tm, const Submission &s)
 {
     if (!c->partitioned) return kmer_rarefaction(c, tm, s);
-    if (!c->kmer_active || s.n == 0) { c->seg_epoch.clear(); return 0; }
+    if (!c->kmer_active || s.n == 0) {
+        // nothing to send: the counts of the submission BEFORE this one must not be read again (faqcs_kmer_outbox_host listed its keys a second
+        // time, faqcs_kmer_forward moved its items a second time)
+        HIPCHK(hipMemsetAsync(c->d_ob, 0, (size_t)c->part_world * 8, c->compute));
+        c->seg_epoch.clear();
+        return 0;
+    }
     if (c->seg_epoch.size() != s.n_seg) return fail(FAQCS_E_INVAL, "faqcs_submit: faqcs_kmer_set_epochs() must give one epoch per segment of the submission");
     if (int rc = c->kg.direct ? kmer_send_pairs(c, tm, s) : kmer_send_items(c, tm, s)) return rc;
     c->seg_epoch.clear();

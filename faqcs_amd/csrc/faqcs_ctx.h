@@ -300,5 +300,6 @@ struct Submission {
 // host functions that cross translation units (file-local before the host side was split: none is exported)
 FAQCS_HIDDEN int fold_pending_now(faqcs_ctx *c);                                   // faqcs_capi.hip
 FAQCS_HIDDEN int enqueue_kmers(faqcs_ctx *c, Timing *tm, const Submission &s);     // faqcs_capi_kmer.hip: the k-mer tail of a submission
+FAQCS_HIDDEN int check_kmers(faqcs_ctx *c, const Submission &s);                   // faqcs_capi_kmer.hip: what enqueue_kmers would refuse, before anything is enqueued
 FAQCS_HIDDEN int resolve_points(faqcs_ctx *c);                                     // faqcs_capi_kmer.hip
 FAQCS_HIDDEN void comm_release(void *comm);                                        // faqcs_capi_comm.hip (ncclCommDestroy)

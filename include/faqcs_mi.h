@@ -855,18 +855,28 @@ int  faqcs_kmer_memory_plan(const faqcs_params *params, uint64_t free_bytes, uin
  * for its epoch) the exchange moves runs of k-mers and the owner combines them; a job with more sampling points goes through (key, epoch)
  * pairs instead -- 16 bytes per occurrence, one atomic per pair on the owner: exact, any --subset, slow. */
 int  faqcs_kmer_partition(faqcs_ctx *ctx, uint32_t rank, uint32_t world, uint32_t n_epochs);
-/* Epoch of every segment of the NEXT submission (which then buckets instead of inserting). */
+/* Epoch of every segment of the NEXT submission (which then buckets instead of inserting).  That submission is refused with FAQCS_E_INVAL
+ * when the epochs do not number its segments, or -- runs of k-mers, not pairs -- when it holds more than 1 000 runs of consecutive segments
+ * with one epoch (a run is one extraction launch; an item has 10 bits for it).  A refused submission is refused before any kernel of it is
+ * launched: nothing of it is trimmed or counted, no k-mer launch is made (only its bytes have been copied to a staging buffer, which the
+ * next submission overwrites), its reads are not in the counter block and the outbox is the one before.  The epochs given for it stay set
+ * until the next faqcs_kmer_set_epochs() or accepted submission. */
 int  faqcs_kmer_set_epochs(faqcs_ctx *ctx, const uint32_t *segment_epoch, uint32_t n_segments);
 /* After a submission: device array of 16-byte items grouped by destination rank 0..world-1 and the number of ITEMS per destination
  * (counts[world]).  Valid until the next submission.  A second call without a submission in between reports nothing to send (all
- * counts 0): a rank of a collective loop whose part of the input was empty does not send the previous outbox again. */
+ * counts 0): a rank of a collective loop whose part of the input was empty does not send the previous outbox again.  A submission
+ * without reads EMPTIES the outbox: behind it faqcs_kmer_outbox_host lists no key and faqcs_kmer_forward moves nothing. */
 int  faqcs_kmer_outbox(faqcs_ctx *ctx, void **d_items, uint64_t *counts);
 /* The canonical keys of EVERY OCCURRENCE of the last submission's outbox, expanded from its items on the host (all destinations; keys ==
  * NULL or cap too small: only the count is returned).  For a caller that owns the table itself, like the reference's trim() seam (MAP<Word,size_t>,
  * trim.cpp:133-135): the key values are an injective re-encoding of the canonical k-mers, so counts and distinct counts
  * are the reference's, the key values are not. */
 int  faqcs_kmer_outbox_host(faqcs_ctx *ctx, uint64_t *keys, uint64_t cap, uint64_t *n_keys);
-/* Owner side: takes n_items received items (device pointer; returns when the buffer may be reused). */
+/* Owner side: takes n_items received items (device pointer; returns when the buffer may be reused).  The items must be the ones a sender
+ * partitioned over the same `world` grouped for THIS rank: bucket b (the top 8 bits of an item's partition) goes to rank (b * world) >> 8,
+ * and rank r owns the buckets ceil(r * 256 / world) .. ceil((r + 1) * 256 / world) - 1 -- the same set for every world up to 64.  An item of
+ * another rank's bucket is NOT detected: its partition is mapped onto this rank's table as if it were its own (modulo 2^32) and the
+ * results of this rank are undefined from there on. */
 int  faqcs_kmer_insert_device(faqcs_ctx *ctx, const void *d_items, uint64_t n_items);
 /* (Replaces, like the calls around it, the per-call merge of thread-local k-mer tables into ONE map, trim.cpp:133-135, for a map that is
  * partitioned over devices.)  The exchange inside ONE process that drives several devices (faqcs_mi --gpus N --kmer_rarefaction): moves the last submission's
