@@ -1,5 +1,5 @@
 """CPU-side checks of host code in the native command line that needs no device: the BGZF reader and the report script
-(`faqcs_mi --bgzf_cat`, `faqcs_mi --report_script`; faqcs_cli.cpp:host_self_check)."""
+(`faqcs_mi --bgzf_cat`, `faqcs_mi --report_script`; csrc/cli/cli_process.h:host_self_check)."""
 import os
 import struct
 import subprocess
@@ -154,7 +154,7 @@ def test_bgzf_reader_reports_what_gzread_reports(tmp_path):
 def test_report_script_is_structurally_sound():
     """No R in the build image: the script the report step pipes into `R --vanilla --silent --slave` has never been rendered (README,
     INTEGRATION.md say so).  What CAN be checked without R: every bracket / quote is balanced outside comments and strings, and every
-    table the script reads is one that write_tables() writes (faqcs_cli.cpp:table_files), under the name the script builds."""
+    table the script reads is one that write_tables() writes (csrc/cli/cli_report.h:table_files), under the name the script builds."""
     import re
 
     r = subprocess.run([CLI, "--report_script", "-1", "a.fastq", "-2", "b.fastq", "-d", "/tmp/out dir", "--prefix", "S1", "--kmer_rarefaction"],

@@ -1967,7 +1967,7 @@ def _write_bgzf(path, data, block=60000, level=4):
 
 
 def test_native_cli_reads_bgzf_in_parallel(tmp_path):
-    """bgzip-compressed inputs are inflated member by member by a thread pool (BgzfReader in faqcs_cli.cpp): same output bytes
+    """bgzip-compressed inputs are inflated member by member by a thread pool (BgzfReader in csrc/cli/cli_input.h): same output bytes
     as from the plain files, and as from the same .gz read through gzread (FAQCS_MI_NO_BGZF=1)."""
     import hashlib
     import struct
