@@ -194,6 +194,12 @@ class KernelTimes(C.Structure):
                 ("kmer_ms", C.c_double), ("kmer_insert_ms", C.c_double)]
 
 
+class PathTallies(C.Structure):
+    """faqcs_path_tallies: which arm of the host orchestration the calls on a context took (host-side counts, faqcs_path_tallies_get)."""
+    _fields_ = [(n, C.c_uint64) for n in ("folds_tail", "folds_aux", "folds_now", "folds_dropped", "slot_stream_waits", "slot_event_syncs",
+                                          "recset_fold_waits", "recset_grow_syncs", "ticket_ring_waits")]
+
+
 RESULT_DTYPE = np.dtype([("start", "<u2"), ("len", "<u2"), ("flags", "<u2"), ("adapter", "<u2")])
 RAREFACTION_DTYPE = np.dtype([("num_seq", "<u8"), ("distinct_kmer", "<u8"), ("total_kmer", "<u8")])
 
@@ -305,6 +311,7 @@ def load_library():
         "faqcs_wait": (i32, [vp, u64]),
         "faqcs_host_alloc": (vp, [C.c_size_t]),
         "faqcs_host_free": (None, [vp]),
+        "faqcs_path_tallies_get": (i32, [vp, C.POINTER(PathTallies)]),
         "faqcs_counters_device": (i32, [vp, C.POINTER(vp), C.POINTER(u64)]),
         "faqcs_counters_export": (i32, [vp, vp, u64]),
         "faqcs_counters_import": (i32, [vp, vp, u64]),
@@ -343,7 +350,12 @@ def load_library():
         "faqcs_debug_words": (i32, [vp, vp, u32]),
         "faqcs_kernel_report": (i32, [vp, C.POINTER(KernelTimes)]),
     }
+    # an alternative build named by FAQCS_MI_LIB (a tuning or checking build of the same kernels) may be older than the observation-only entry
+    # points: it loads without them, and a caller that asks for one gets ctypes' AttributeError.  The product library must export them all
+    observers = {"faqcs_path_tallies_get"} if os.environ.get("FAQCS_MI_LIB") else set()
     for name, (res, args) in sig.items():
+        if name in observers and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)  # AttributeError == a symbol the header declares is missing
         fn.restype = res
         fn.argtypes = args

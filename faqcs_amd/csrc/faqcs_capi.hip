@@ -349,7 +349,8 @@ static int enqueue_trim(faqcs_ctx *c, Timing &t, const Submission &s, const uint
     const uint32_t n = s.n;
     HIPCHK(hipEventRecord(t.a, c->compute));
     // the records of the launch BEFORE this one: this launch's blocks fold them when they run out of reads, if its kernel can (trim_lds with
-    // a block of at least 122 KB of LDS: the 2x100 ... 2x150 variants); FAQCS_TAIL_FOLD=0: never (A/B)
+    // a block of at least 122 KB of LDS and one-word records: the shapes of 105 ... 152 and of 153 ... 252 bases, TrimLdsShape::folds_tail --
+    // not the 4-lane shapes, not 77 ... 104, not 253 ... 304); FAQCS_TAIL_FOLD=0: never (A/B)
     const bool tail_on = env_on("FAQCS_TAIL_FOLD"); // (read at every submission, like FAQCS_TRIM_LONG below: a test runs one engine with it and one without)
     const bool offer_fold = c->pending_fold >= 0 && !c->pending_wide && tail_on;
     DevParams dp = c->dp;
@@ -361,9 +362,9 @@ static int enqueue_trim(faqcs_ctx *c, Timing &t, const Submission &s, const uint
     dp.wide_records = plan.wide_records;
     const int set = (int)(c->n_enqueued++ & 1);
     faqcs_ctx::RecSet &rs = c->rec[set];
-    if (rs.used) { HIPCHK(hipStreamWaitEvent(c->compute, rs.folded, 0)); rs.used = false; } // (a fold of the set's previous records on the aux stream)
+    if (rs.used) { HIPCHK(hipStreamWaitEvent(c->compute, rs.folded, 0)); rs.used = false; ++c->tally.recset_fold_waits; } // (a fold of the set's previous records on the aux stream)
     const size_t need = plan.records_needed;
-    if (need > rs.pre.cap) { HIPCHK(hipStreamSynchronize(c->aux)); HIPCHK(hipStreamSynchronize(c->compute)); } // (the set's old records may still be read: by the fold kernel, or by the launch before this one)
+    if (need > rs.pre.cap) { HIPCHK(hipStreamSynchronize(c->aux)); HIPCHK(hipStreamSynchronize(c->compute)); ++c->tally.recset_grow_syncs; } // (the set's old records may still be read: by the fold kernel, or by the launch before this one)
     HIPCHK(rs.pre.reserve(need)); HIPCHK(rs.post.reserve(need));
     if (offer_fold) {
         const faqcs_ctx::RecSet &ps = c->rec[c->pending_fold];
@@ -385,7 +386,8 @@ static int enqueue_trim(faqcs_ctx *c, Timing &t, const Submission &s, const uint
                                             c->d_counters + c->lay.post_comp, c->n_cu, c->aux));
             HIPCHK(hipEventRecord(ps.folded, c->aux));
             ps.used = true;
-        }
+            ++c->tally.folds_aux;
+        } else ++c->tally.folds_tail;
         c->pending_fold = -1;
     }
     static const bool no_comp = [] { const char *e = getenv("FAQCS_DIAG_NO_COMPOSITION"); return e && atoi(e) != 0; }(); // (diagnostic, wrong composition tables: what the fold costs a step)
@@ -447,12 +449,12 @@ extern "C" int faqcs_submit_async(faqcs_ctx *c, const faqcs_batch *b, faqcs_read
     const size_t bytes = (size_t)(o1 - o0);
     faqcs_ctx::Slot &sl = c->slot[c->n_submits & 1];
     hipEvent_t tk = c->ticket_ev[c->n_submits & 7];
-    if (c->n_submits >= 8) HIPCHK(hipEventSynchronize(tk)); // the ticket ring is 8 deep
+    if (c->n_submits >= 8) { HIPCHK(hipEventSynchronize(tk)); ++c->tally.ticket_ring_waits; } // the ticket ring is 8 deep
     // the slot may still feed the kernels of submission k-2: growing it (hipFree) needs them finished, reusing it
     // only needs the copy stream to wait for them
     if (sl.used) {
-        if (bytes + FAQCS_ARENA_PAD_BEFORE + FAQCS_ARENA_PAD_AFTER > sl.seq.cap || (size_t)n + 1 > sl.off.cap || (b->terminal_n && (size_t)n + 64 > sl.tn.cap)) HIPCHK(hipEventSynchronize(sl.done));
-        else HIPCHK(hipStreamWaitEvent(c->copy, sl.done, 0));
+        if (bytes + FAQCS_ARENA_PAD_BEFORE + FAQCS_ARENA_PAD_AFTER > sl.seq.cap || (size_t)n + 1 > sl.off.cap || (b->terminal_n && (size_t)n + 64 > sl.tn.cap)) { HIPCHK(hipEventSynchronize(sl.done)); ++c->tally.slot_event_syncs; }
+        else { HIPCHK(hipStreamWaitEvent(c->copy, sl.done, 0)); ++c->tally.slot_stream_waits; }
     }
     HIPCHK(sl.seq.reserve(bytes + FAQCS_ARENA_PAD_BEFORE + FAQCS_ARENA_PAD_AFTER)); HIPCHK(sl.qual.reserve(bytes + FAQCS_ARENA_PAD_BEFORE + FAQCS_ARENA_PAD_AFTER)); HIPCHK(sl.off.reserve((size_t)n + 1));
     if (b->terminal_n) HIPCHK(sl.tn.reserve((size_t)n + 64));
@@ -493,6 +495,13 @@ extern "C" int faqcs_wait(faqcs_ctx *c, uint64_t ticket)
     if (ticket >= c->n_submits) return fail(FAQCS_E_INVAL, "faqcs_wait: unknown ticket");
     if (ticket + 8 < c->n_submits) return 0; // its event slot has been recycled: the submission finished long ago
     HIPCHK(hipEventSynchronize(c->ticket_ev[ticket & 7]));
+    return 0;
+}
+
+extern "C" int faqcs_path_tallies_get(const faqcs_ctx *c, faqcs_path_tallies *out)
+{
+    if (!c || !out) return fail(FAQCS_E_INVAL, "faqcs_path_tallies_get: null argument");
+    *out = c->tally;
     return 0;
 }
 
@@ -540,6 +549,7 @@ int fold_pending_now(faqcs_ctx *c)
     HIPCHK(faqcs_launch_composition(ps.pre.p, ps.post.p, c->pending_n, c->pending_wide, c->d_norm, c->d_counters + c->lay.pre_comp,
                                     c->d_counters + c->lay.post_comp, c->n_cu, c->compute));
     c->pending_fold = -1;
+    ++c->tally.folds_now;
     return 0;
 }
 
@@ -628,6 +638,7 @@ extern "C" int faqcs_reset_counters(faqcs_ctx *c)
     if (!c) return fail(FAQCS_E_INVAL, "null ctx");
     HIPCHK(hipSetDevice(c->device));
     // (records that are still to be folded belong to the job that ends here: they are dropped with its block -- a caller reads the block first)
+    if (c->pending_fold >= 0) ++c->tally.folds_dropped;
     c->pending_fold = -1;
     HIPCHK(hipStreamSynchronize(c->aux));
     HIPCHK(hipMemsetAsync(c->d_counters, 0, c->lay.total * sizeof(uint64_t), c->compute));

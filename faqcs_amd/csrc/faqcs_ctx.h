@@ -216,6 +216,8 @@ struct faqcs_ctx {
     bool pending_wide = false;
     uint32_t *d_fold_claim = nullptr;
     hipStream_t aux = nullptr;
+    // which arm of the host orchestration a call took, counted where the branch is taken (faqcs_path_tallies_get: a test asserts the arm it is about)
+    faqcs_path_tallies tally{};
     // rarefaction state (trim.cpp:157-185): host-deterministic from read counts, values filled from the device
     uint64_t total_number = 0;
     int kmer_active = 0;

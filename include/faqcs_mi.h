@@ -38,7 +38,7 @@ extern "C" {
  * and faqcs_gunzip_device / faqcs_gunzip_host (ordinary gzip to that text; FAQCS_INFLATE_E_SERIAL is theirs alone),
  * and faqcs_deflate_device / faqcs_deflate_host (text to BGZF members), and faqcs_pair_device / faqcs_pair_host /
  * faqcs_render_pair_device / faqcs_render_pair_host (the two mates of a paired run from two batches), and faqcs_detect_device /
- * faqcs_detect_host / faqcs_first_error_device / faqcs_first_error_host / faqcs_set_input_quality_offset (the decisions around trim()). */
+ * faqcs_detect_host / faqcs_first_error_device / faqcs_first_error_host / faqcs_set_input_quality_offset (the decisions around trim()), and faqcs_path_tallies_get (read-only, a structure of its own). */
 #define FAQCS_ABI_VERSION 2
 
 /* FilterStat enum order, FaQCs.h:46-75 */
@@ -761,6 +761,22 @@ int  faqcs_submit_async(faqcs_ctx *ctx, const faqcs_batch *batch, faqcs_read_res
 int  faqcs_wait(faqcs_ctx *ctx, uint64_t ticket);
 void *faqcs_host_alloc(size_t bytes);
 void faqcs_host_free(void *p);
+
+/* Which arm of the host orchestration the calls on a context have taken since faqcs_create(): plain host-side counts, incremented where
+ * the branch is taken; no kernel knows of them and nothing resets them.  Read-only, never waits, touches no stream.  They exist so that
+ * a test can state which path it ran (tests/submit_edges.py predicts every one of them from the schedule of calls alone). */
+typedef struct faqcs_path_tallies {
+    uint64_t folds_tail;         /* composition records of launch k-1 handed to launch k's blocks (comp_fold_tail) */
+    uint64_t folds_aux;          /* ... to composition_histogram on the aux stream, beside launch k */
+    uint64_t folds_now;          /* ... folded on the compute stream: faqcs_sync / _finish, faqcs_counters_export / _import, the collectives */
+    uint64_t folds_dropped;      /* ... dropped with the block by faqcs_reset_counters */
+    uint64_t slot_stream_waits;  /* faqcs_submit_async: a staging slot reused as it is, the copy stream waits for submission k-2 */
+    uint64_t slot_event_syncs;   /* ... regrown: the host waits for submission k-2 */
+    uint64_t recset_fold_waits;  /* a record set reused while its aux fold may still run: the compute stream waits for `folded` */
+    uint64_t recset_grow_syncs;  /* a record set regrown: the host waits for the aux and the compute stream */
+    uint64_t ticket_ring_waits;  /* faqcs_submit_async: the host waits for the submission that held this ticket's event eight calls ago */
+} faqcs_path_tallies;
+int  faqcs_path_tallies_get(const faqcs_ctx *ctx, faqcs_path_tallies *out);
 
 /* Options::quality is mutable during a run: the NextSeq check bumps -q to 20 (FaQCs.cpp:272-277,404-414).
  * Takes effect for batches submitted afterwards. */

@@ -25,6 +25,14 @@ def test_exports_every_declared_symbol(lib):
     missing = [s for s in declared if not hasattr(lib, s)]
     assert not missing, missing
     assert lib.faqcs_abi_version() == capi.ABI_VERSION
+    assert "faqcs_path_tallies_get" in declared and "faqcs_path_tallies_get" in lib._faqcs_symbols
+
+
+def test_path_tallies_entry_point(lib):
+    """An additive, read-only entry point with a structure of its own (the ABI number stands): nine uint64 fields, and no context is an error."""
+    assert C.sizeof(capi.PathTallies) == 9 * 8
+    t = capi.PathTallies()
+    assert lib.faqcs_path_tallies_get(None, C.byref(t)) == capi.E_INVAL and b"faqcs_path_tallies_get" in lib.faqcs_last_error()
 
 
 @pytest.mark.parametrize("R,na", [(150, 0), (256, 10), (1024, 12)])

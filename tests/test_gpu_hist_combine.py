@@ -3,17 +3,23 @@ cells of a trim_lds chunk's epilogue -- read length, int(average quality), bases
 composition fold.  Batches built so that the lanes of a wave meet on one cell, on a few, on every bin, or on none, at the four shapes of
 trim_lds (4, 8 and 16 lanes per read; 64 and 32 reads per chunk), every counter against the oracle.
 
-Each case runs three launches in one engine: compare_engines() reads the counters behind the first, which folds its composition records
-with the standalone kernel (composition_histogram); the third launch folds the records of the second in the tail of its blocks
-(comp_fold_tail) where the shape's blocks do that.  Then the same again in a fresh engine with FAQCS_TAIL_FOLD=0, where
-composition_histogram folds every launch's records beside the next launch."""
+Each case runs two passes of three launches, each pass under both values of FAQCS_TAIL_FOLD:
+    synced     HipEngine.process() is faqcs_submit + faqcs_sync, and faqcs_sync folds what is pending: composition_histogram on the compute
+               stream folds every launch's records, whatever FAQCS_TAIL_FOLD says.  This pass is about the epilogue's cells.
+    unsynced   the same three launches through faqcs_submit_device on a fresh engine with no sync between them, then one faqcs_finish:
+               the second and the third launch fold the records of the one before in the tail of their blocks (comp_fold_tail) where the
+               shape's blocks do that (105 ... 252 bases), else -- and always with FAQCS_TAIL_FOLD=0 -- composition_histogram folds them on
+               the aux stream beside the launch; the last launch's records are folded by faqcs_finish.  faqcs_path_tallies_get() says so."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
 from faqcs_amd import _capi as capi
 from faqcs_amd import driver
 from faqcs_amd.options import parse_args
-from test_gpu_parity import SEED, compare_engines
+import trim_dispatch_cases as td
+from test_gpu_parity import SEED, compare_engines, hip_factory
 
 pytestmark = pytest.mark.gpu
 
@@ -57,6 +63,44 @@ def _check(reads, monkeypatch, args=()):
             tail_fold, len(bad), bad[0], c1[bad[0]], c2[bad[0]])
         hip.close()
         ora.close()
+        _unsynced(opt, args, seq, qual, offset, seg, tail_fold, c2)  # (the oracle's block behind the same three launches)
+
+
+def _unsynced(opt, args, seq, qual, offset, seg, tail_fold, c2, launches=3):
+    """The same batch `launches` times through faqcs_submit_device with nothing between the calls, one faqcs_finish: the whole block against
+    the oracle's, and the arms the folds took."""
+    import torch
+
+    from faqcs_amd.engine import _check as check
+
+    n, longest = len(offset) - 1, int(np.diff(offset.astype(np.int64)).max())
+    dev = torch.device("cuda:0")
+    front, total = 64, int(offset[-1])
+    arenas = []
+    for a in (seq, qual):
+        h = np.full(front + total + 128, ord("N"), np.uint8)
+        h[front:front + total] = a[:total]
+        arenas.append(torch.from_numpy(h).to(dev))
+    d_off = torch.from_numpy(np.ascontiguousarray(offset, np.uint32).view(np.int32)).to(dev)
+    res = torch.zeros((n, 4), dtype=torch.int16, device=dev)
+    torch.cuda.synchronize()
+    hip = hip_factory(opt, 256, 33)
+    try:
+        seg = np.ascontiguousarray(seg, np.uint32)
+        b = capi.Batch(arenas[0].data_ptr() + front, arenas[1].data_ptr() + front, d_off.data_ptr(), n, len(seg) - 1, seg.ctypes.data, longest, None)
+        for _ in range(launches):
+            check(hip.lib, hip.lib.faqcs_submit_device(hip.ctx, C.byref(b), res.data_ptr()))
+        c1 = hip.counters()
+        bad = np.nonzero(c1 != c2)[0]
+        assert len(bad) == 0, "FAQCS_TAIL_FOLD=%s, %d launches without a sync: counter block differs in %d places, first at %d: hip=%d oracle=%d" % (
+            tail_fold, launches, len(bad), bad[0], c1[bad[0]], c2[bad[0]])
+        t = capi.PathTallies()
+        assert hip.lib.faqcs_path_tallies_get(hip.ctx, C.byref(t)) == 0
+        folds = bool(td.expected_plan(dict(td.option_fields(list(args)), fold_n=n), longest, n, 256, td.DEFAULT_SWITCHES)["folds_tail"]) and tail_fold is None
+        assert (t.folds_tail, t.folds_aux, t.folds_now, t.folds_dropped) == ((launches - 1, 0, 1, 0) if folds else (0, launches - 1, 1, 0)), \
+            "FAQCS_TAIL_FOLD=%s, longest read %d: %d tail, %d aux, %d now" % (tail_fold, longest, t.folds_tail, t.folds_aux, t.folds_now)
+    finally:
+        hip.close()
 
 
 @pytest.mark.parametrize("n", [64, 65, 130])

@@ -1831,11 +1831,14 @@ def test_dispatcher_picks_the_documented_trim_kernel(L, args, kernel):
 
 def test_one_context_through_every_kind_of_trim_plan():
     """Submissions of 300 reads on ONE context whose longest reads have 150, 300, 305, 1 100 and 150 bases, and 150 once more: trim_lds with
-    one-word records, trim_lds with two-word records, trim_filter_accumulate, trim_long and back.  Each launch folds -- or leaves to
-    composition_histogram -- the records of the one before it (faqcs_ctx::pending_fold, pending_wide): the second fold is of one-word records
-    beside a launch that writes two-word ones, the next two of two-word records, trim_long leaves none and keeps its scratch in a record array,
-    and the last launch (the sixth submission is there for it) folds the fifth's records in its blocks' tails.  The kernel after every submission,
-    and the whole counter block at the end against the oracle's."""
+    one-word records, trim_lds with two-word records, trim_filter_accumulate, trim_long and back.  Two passes.  The first syncs behind every
+    submission (HipEngine.process) and asks for the kernel's name: faqcs_sync folds each launch's records at once, on the compute stream, so
+    this pass checks the kernels and the per-read results.  The second, on a fresh engine, takes the six submissions through faqcs_submit
+    with NO sync and one faqcs_finish: there each launch folds -- or leaves to composition_histogram on the aux stream -- the records of
+    the one before it (faqcs_ctx::pending_fold, pending_wide): one-word records beside a launch that writes two-word ones, two-word records
+    beside trim_filter_accumulate and beside trim_long, trim_long leaves none and keeps its scratch in a record array, and the sixth launch
+    folds the fifth's records in its blocks' tails; faqcs_path_tallies_get() must say exactly that.  The whole counter block at the end of
+    either pass against the oracle's."""
     import ctypes as C
 
     from oracle_engine import OracleEngine
@@ -1845,14 +1848,34 @@ def test_one_context_through_every_kind_of_trim_plan():
     opt = parse_args(["-u", "x", "-d", "y"])
     rng = np.random.Generator(np.random.PCG64([6, SEED]))
     hip, ora = hip_factory(opt, 2048, 33), OracleEngine(opt, 2048, 33)
+    batches, wanted = [], []
     for L, kernel in [(150, "trim_lds"), (300, "trim_lds"), (305, "trim_filter_accumulate"), (1100, "trim_long"), (150, "trim_lds"), (150, "trim_lds")]:
         reads = random_batch(rng, 299, L, "ragged") + [(b"@x", make_uniform(rng, L), bytes((rng.integers(20, 41, L) + 33).astype(np.uint8)))]
         seq, qual, offset, seg = driver.pack_segments([reads])
-        assert (hip.process(seq, qual, offset, seg) == ora.process(seq, qual, offset, seg)).all()
+        batches.append((seq, qual, np.ascontiguousarray(offset, np.uint32), np.ascontiguousarray(seg, np.uint32)))
+        wanted.append(ora.process(seq, qual, offset, seg))
+        assert (hip.process(seq, qual, offset, seg) == wanted[-1]).all()
         kt = capi.KernelTimes()
         assert hip.lib.faqcs_kernel_report(hip.ctx, C.byref(kt)) == 0
         assert (kt.trim_kernel or b"").decode() == kernel
     assert (hip.counters() == ora.counters()).all()
+    hip.close()
+    # the second pass: nothing waits between the six submissions
+    from faqcs_amd.engine import _check
+
+    hip = hip_factory(opt, 2048, 33)
+    got = [np.zeros(len(b[2]) - 1, dtype=capi.RESULT_DTYPE) for b in batches]
+    for (seq, qual, offset, seg), res in zip(batches, got):
+        b = capi.Batch(seq.ctypes.data, qual.ctypes.data, offset.ctypes.data, len(offset) - 1, len(seg) - 1, seg.ctypes.data, 0, None)
+        _check(hip.lib, hip.lib.faqcs_submit(hip.ctx, C.byref(b), res.ctypes.data))
+    assert (hip.counters() == ora.counters()).all()
+    assert all((g == w).all() for g, w in zip(got, wanted))
+    t = capi.PathTallies()
+    assert hip.lib.faqcs_path_tallies_get(hip.ctx, C.byref(t)) == 0
+    # 150 -> 300: aux (a 16-lane shape of two-word records cannot fold); 300 -> 305 and 305 -> 1 100: aux (two-word records); 1 100 -> 150: nothing is pending;
+    # 150 -> 150: the tail; the sixth launch's records: faqcs_finish
+    assert (t.folds_aux, t.folds_tail, t.folds_now, t.folds_dropped) == (3, 1, 1, 0)
+    hip.close()
 
 
 def make_uniform(rng, L):

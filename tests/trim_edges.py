@@ -1057,7 +1057,9 @@ def composition_cases():
     C = []
     base = ["--min_L", "1", "--lc", "1.0", "-n", "2000"]
     # row by row on one engine, the 253 .. 304 row in two halves behind the first row: one-word records (reads up to 256 bases) and two-word records
-    # follow each other in all four orders; each launch folds or hands on the records of the one before, and a small last submission flushes
+    # follow each other in all four orders.  (The GPU test syncs behind every submission, and faqcs_sync folds what is pending: composition_histogram on
+    # the compute stream folds every row's records, one-word or two-word, at once -- no launch folds or hands on the records of the one before it here;
+    # the launches that do are the unsynced schedules of tests/submit_edges.py.)  The small last submission is one more launch behind the widest rows
     order = [LDS_ROWS[0][:2], (253, 280), (281, 304)] + [r[:2] for r in LDS_ROWS[1:5]]
     subs = [[[rd(b"A" * c + b"T" * (n - c)) for n in range(lo, hi + 1) for c in range(n + 1)]] for lo, hi in order]
     subs.append([[rd(rb(30, 1))]])
