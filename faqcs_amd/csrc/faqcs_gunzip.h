@@ -1,7 +1,8 @@
 // faqcs_gunzip.h -- faqcs_gunzip_device / faqcs_gunzip_host (include/faqcs_mi.h): ordinary gzip -- members of any
 // size, no index -- inflated by pieces.  The SAME text compiles for the host statement (faqcs_host.cpp), the sanitizer tool
-// (tools/gunzip_host_fuzz.cpp) and gfx950 (faqcs_gunzip_kernel.hip), as faqcs_inflate.h does, and it builds on that file: BitReader,
-// build_table, decode_symbol, the length / distance arithmetic and the CRC are used as they are, inflate_member is not touched.
+// (tools/gunzip_host_fuzz.cpp) and gfx950 (faqcs_gunzip_kernel.hip), as faqcs_inflate.h does, and it builds on that file: the member header,
+// BitReader, build_table, decode_symbol, the length / distance arithmetic, the CRC arithmetic and the host's Sink are that file's.  gz_run
+// is inflate_member's block decoder once more, with its own bounds, statuses and stops: a rule changed in one is to be changed in the other.
 //
 //   pieces    the compressed bytes are cut every piece_bytes bytes (a grid over the whole input).  The wave of a grid piece PROBES its range for
 //             the first bit position that can begin a non-final dynamic-Huffman block (plausible_block: the rules of faqcs_pargz.h) and whose
@@ -21,7 +22,7 @@
 //             symbols get a front of 32 768 that holds the carried window as bytes, so the first piece's markers resolve like any other's, and
 //             with final = 0 the walk stops at the last block boundary that is resident; the CRC so far and this call's share are folded as
 //             zlib's crc32_combine folds them.
-// A Sink here is faqcs_inflate.h's with 16-bit output and one more member: umin(v), the smallest v of the cooperating lanes.
+// A Sink here is faqcs_inflate.h's with 16-bit output.
 #pragma once
 #include "faqcs_inflate.h"
 
@@ -46,40 +47,8 @@ struct Slice { uint32_t begin, n, piece, pad; };
 struct SliceResult { uint32_t crc, bad; }; // the slice's share of its member's CRC-32 | a marker in front of the member
 struct Pow { uint32_t x2n[36]; };          // x^(2^k) modulo the gzip polynomial, reflected: 8 x 2^32 bits
 
+static_assert(WIN == inf::MAX_DIST, "a marker's k counts from the window's first byte");
 static_assert(sizeof(Piece) == 32 && sizeof(ChainPiece) == 32 && sizeof(Slice) == 16, "the records the host and the device exchange");
-
-// ---- the member header (RFC 1952) -------------------------------------------------------------------------------------------------------
-// What stands at w[0 .. have), the first bytes of comp[p ..); all: these are all the bytes there are.
-//   H_OK        a header of hlen bytes, the deflate stream behind it          H_END      not gzip: the data ends here, without an error
-//   H_HEADER    CM != 8 or a reserved FLG bit                                 H_PARTIAL  sound as far as it goes, and it ends early
-//   H_MORE      (all = false) the header is longer than the window
-enum { H_OK = 0, H_END, H_HEADER, H_PARTIAL, H_MORE };
-INF_HD int gz_header(const uint8_t *w, uint64_t have, bool all, uint32_t &hlen)
-{
-    hlen = 0;
-    const int shrt = all ? H_PARTIAL : H_MORE;
-    if (!have) return shrt;
-    if (w[0] != 31 || (have >= 2 && w[1] != 139)) return H_END;
-    if (have >= 3 && w[2] != 8) return H_HEADER;
-    if (have >= 4 && (w[3] & 0xe0u)) return H_HEADER;
-    if (have < 10) return shrt;
-    const uint32_t flg = w[3];
-    uint64_t q = 10;
-    if (flg & 4u) { // FEXTRA
-        if (have < 12) return shrt;
-        q = 12 + (uint64_t)inf::le16(w + 10);
-    }
-    for (uint32_t bit = 8; bit <= 16; bit <<= 1) // FNAME, FCOMMENT: zero-terminated
-        if (flg & bit) {
-            while (q < have && w[q]) ++q;
-            if (q >= have) return shrt;
-            ++q;
-        }
-    if (flg & 2u) q += 2; // FHCRC: skipped, not verified
-    if (q > have) return shrt;
-    hlen = (uint32_t)q;
-    return H_OK;
-}
 
 // ---- the probe --------------------------------------------------------------------------------------------------------------------------
 INF_HD uint64_t peek(const uint8_t *in, uint64_t n, uint64_t bit) // 57 bits at `bit`; zeros behind the input
@@ -365,39 +334,6 @@ INF_HD uint32_t narrow_slice(const uint16_t *sym, uint8_t *text, const Slice &s,
     return bad;
 }
 
-inline void pow_init(Pow &P)
-{
-    uint32_t p = 0x40000000u; // x^1
-    for (uint32_t k = 0; k < 36; ++k) { P.x2n[k] = p; p = inf::multmodp(p, p); }
-}
-INF_HD uint32_t x8n_modp(const Pow &P, uint64_t n) // x^(8 n), n < 2^33
-{
-    uint32_t p = 0x80000000u;
-    for (uint32_t k = 3; n; n >>= 1, ++k)
-        if (n & 1u) p = inf::multmodp(P.x2n[k], p);
-    return p;
-}
-
-// ---- the host as a Sink -------------------------------------------------------------------------------------------------------------
-struct HostSymSink {
-    uint16_t *out;
-    uint32_t lane() const { return 0; }
-    uint32_t lanes() const { return 1; }
-    void sync() {}
-    uint32_t uni(uint32_t v) const { return v; }
-    uint32_t umin(uint32_t v) const { return v; }
-    void lit(uint32_t o, uint32_t v) { out[o] = (uint16_t)v; }
-    void match(uint32_t o, uint32_t len, uint32_t dist)
-    {
-        for (uint32_t i = 0; i < len; ++i) {
-            const int64_t s = (int64_t)o - dist + (dist >= len ? i : i % dist);
-            out[o + i] = s < 0 ? (uint16_t)(0x8000u | (uint32_t)(WIN + s)) : out[s];
-        }
-    }
-    void stored(uint32_t o, const uint8_t *src, uint32_t len) { for (uint32_t i = 0; i < len; ++i) out[o + i] = src[i]; }
-    void flush() {}
-};
-
 // ---- the chain: host code of both forms -------------------------------------------------------------------------------------------------
 struct Info { uint64_t n_bytes, consumed; uint32_t n_members, overflow; int32_t error; uint32_t n_pieces, n_fixups, n_rounds; };
 // open: 0, or the phase in which the call leaves the member (final = 0); end_bit: where this call leaves it (open), behind its trailer (not)
@@ -454,18 +390,18 @@ int gunzip_run(Backend &B, uint64_t n_comp, uint32_t piece_bytes, uint32_t max_r
         uint64_t cur = st0.bit, next = 0;
         if (!cont) {
             uint32_t hlen = 0;
-            int h = H_PARTIAL;
+            int h = inf::H_PARTIAL;
             for (uint64_t have = 512;; have *= 8) { // the header: a window of what follows p, widened while the header is longer
                 const uint64_t avail = n_comp - p, take = have < avail ? have : avail;
                 if (!take) break;
                 win.resize(take);
                 if (int rc = B.fetch(p, (uint32_t)take, win.data())) return rc;
-                h = gz_header(win.data(), take, take == avail, hlen);
-                if (h != H_MORE) break;
+                h = inf::gz_header(win.data(), take, take == avail, hlen);
+                if (h != inf::H_MORE) break;
             }
-            if (p == n_comp || h == H_END) { info.consumed = h == H_END && p < n_comp ? n_comp : p; break; }
-            if (h == H_PARTIAL && !final) { info.consumed = p; break; } // the rest of the header comes with the next call
-            if (h != H_OK) { info.error = h == H_HEADER ? (int32_t)inf::ST_E_HEADER : (int32_t)inf::ST_E_TRUNCATED; info.consumed = p; break; }
+            if (p == n_comp || h == inf::H_END) { info.consumed = h == inf::H_END && p < n_comp ? n_comp : p; break; }
+            if (h == inf::H_PARTIAL && !final) { info.consumed = p; break; } // the rest of the header comes with the next call
+            if (h != inf::H_OK) { info.error = h == inf::H_HEADER ? (int32_t)inf::ST_E_HEADER : (int32_t)inf::ST_E_TRUNCATED; info.consumed = p; break; }
             cur = 8 * (p + hlen);
         }
         uint32_t rounds = 0, err = 0;
@@ -525,13 +461,13 @@ int gunzip_run(Backend &B, uint64_t n_comp, uint32_t piece_bytes, uint32_t max_r
     if (!chain.empty())
         if (int rc = B.write(chain, members, F, st0.phase == PH_STREAM ? st0.window_bytes : 0u, (uint32_t)total, res)) return rc;
     Pow pw;
-    pow_init(pw);
+    inf::x2n_fill(pw.x2n, 36);
     size_t n_good = members.size();
     for (size_t k = 0; k < members.size(); ++k) { // CRC and length are looked at last
         const MemberRec &m = members[k];
         const bool carried = k == 0 && st0.phase != PH_BETWEEN;
         // what zlib's crc32_combine makes of the CRC the calls in front carried and this call's share
-        if (carried) res[k].crc ^= inf::multmodp(x8n_modp(pw, m.len), st0.crc);
+        if (carried) res[k].crc ^= inf::multmodp(inf::x8n_modp(pw.x2n, m.len), st0.crc);
         const uint64_t len = (carried ? st0.member_bytes : 0) + m.len;
         const int32_t st = res[k].bad ? (int32_t)inf::ST_E_DATA : m.open ? 0 : (uint32_t)len != m.isize ? (int32_t)inf::ST_E_LENGTH : res[k].crc != m.crc ? (int32_t)inf::ST_E_CRC : 0;
         if (st) { info.error = st; info.n_members = (uint32_t)k; info.n_bytes = m.text_begin; info.consumed = m.header_at; n_good = k; break; }
@@ -585,15 +521,15 @@ struct HostBackend {
     std::vector<uint16_t> sym;
     uint8_t *window = nullptr; // faqcs_gunzip_stream_host: the caller's WIN bytes
     inf::Tables T;
-    HostBackend(const uint8_t *c, uint64_t n, uint32_t pb) : comp(c), n_comp((uint32_t)n), piece_bytes(pb ? pb : DEFAULT_PIECE) { HostSymSink S{nullptr}; inf::crc_init(T, S); }
+    HostBackend(const uint8_t *c, uint64_t n, uint32_t pb) : comp(c), n_comp((uint32_t)n), piece_bytes(pb ? pb : DEFAULT_PIECE) { inf::HostSink<uint16_t> S{nullptr}; inf::crc_init(T, S); }
     int fetch(uint64_t p, uint32_t n, uint8_t *dst) { memcpy(dst, comp + p, n); return 0; }
     int count_grid(Piece *grid, uint32_t n_grid)
     {
-        HostSymSink S{nullptr};
+        inf::HostSink<uint16_t> S{nullptr};
         for (uint32_t g = 0; g < n_grid; ++g) count_piece(comp, n_comp, piece_bytes, grid[g], T, S);
         return 0;
     }
-    int count_forced(Piece &pc) { HostSymSink S{nullptr}; count_piece(comp, n_comp, piece_bytes, pc, T, S); return 0; }
+    int count_forced(Piece &pc) { inf::HostSink<uint16_t> S{nullptr}; count_piece(comp, n_comp, piece_bytes, pc, T, S); return 0; }
     int write(const std::vector<ChainPiece> &chain, const std::vector<MemberRec> &members, uint32_t front, uint32_t window_bytes, uint32_t total,
               std::vector<MemberResult> &res)
     {
@@ -601,20 +537,20 @@ struct HostBackend {
         for (uint32_t i = WIN - window_bytes; i < WIN && window_bytes; ++i) sym[i] = window[i];
         std::vector<uint32_t> dst(chain.size()), rbad(chain.size());
         text.assign((size_t)total, 0);
-        for (size_t k = 0; k < chain.size(); ++k) { HostSymSink S{sym.data() + chain[k].pos}; dst[k] = decode_piece(comp, n_comp, chain[k], T, S); }
+        for (size_t k = 0; k < chain.size(); ++k) { inf::HostSink<uint16_t> S{sym.data() + chain[k].pos}; dst[k] = decode_piece(comp, n_comp, chain[k], T, S); }
         for (size_t k = 0; k < chain.size(); ++k) rbad[k] = resolve_piece(sym.data(), chain[k], 0, 1);
         std::vector<Slice> slices;
         make_slices(chain, slices);
         std::vector<SliceResult> sres(slices.size());
         Pow pw;
-        pow_init(pw);
+        inf::x2n_fill(pw.x2n, 36);
         for (size_t s = 0; s < slices.size(); ++s) {
             const Slice &sl = slices[s];
             const ChainPiece &c = chain[sl.piece];
             sres[s].bad = narrow_slice(sym.data(), text.data(), sl, c, front, 0, 1);
             uint32_t crc = 0;
             for (uint32_t l = 0; l < inf::CRC_LANES; ++l) crc ^= inf::crc_slice(T, text.data() + (sl.begin - front), sl.n, l);
-            sres[s].crc = inf::multmodp(x8n_modp(pw, (uint64_t)c.member_end - (sl.begin + sl.n)), crc);
+            sres[s].crc = inf::multmodp(inf::x8n_modp(pw.x2n, (uint64_t)c.member_end - (sl.begin + sl.n)), crc);
         }
         fold_results(chain, members, slices, sres.data(), dst.data(), rbad.data(), res);
         return 0;

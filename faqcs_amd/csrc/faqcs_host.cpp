@@ -241,7 +241,7 @@ extern "C" int faqcs_inflate_host(const uint8_t *comp, uint64_t n_comp, const ui
     if (!info.overflow) {
         std::vector<uint8_t> one(inf::MAX_ISIZE);
         std::unique_ptr<inf::Tables> T(new inf::Tables);
-        inf::HostSink S{one.data()};
+        inf::HostSink<uint8_t> S{one.data()};
         inf::crc_init(*T, S);
         uint64_t pos = 0;
         bool bad = false;

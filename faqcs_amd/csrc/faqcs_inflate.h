@@ -1,19 +1,23 @@
-// faqcs_inflate.h -- the decoder core of faqcs_inflate_device / faqcs_inflate_host (include/faqcs_mi.h): BGZF member header, canonical
-// Huffman tables with zlib's acceptance rules, symbol decode, length / distance arithmetic, the block loop and the CRC-32 arithmetic; at
-// the end, the BSIZE walk of faqcs_bgzf_index_host and the per-position decision it shares with faqcs_bgzf_index_device's kernels.
+// faqcs_inflate.h -- the decoder core of faqcs_inflate_device / faqcs_inflate_host and of the piece-wise gunzip (faqcs_gunzip.h): the gzip member
+// header, canonical Huffman tables with zlib's acceptance rules, symbol decode, length / distance arithmetic, the block loop of a BGZF
+// member (faqcs_gunzip.h's gz_run is the same loop with a piece's bounds and stops) and the CRC-32 arithmetic; at the end, the BSIZE walk of
+// faqcs_bgzf_index_host and the per-position decision it shares with faqcs_bgzf_index_device's kernels.
 // The SAME text compiles for the host (faqcs_host.cpp: faqcs_inflate_host; tools/inflate_host_fuzz.cpp under the sanitizers) and for
-// gfx950 (faqcs_inflate_kernel.hip), the way faqcs_skm.h does: every bound the decoder checks -- input that runs out, a distance in
-// front of the member, output beyond ISIZE -- is checked HERE, before a Sink is asked to move a byte, so what the CPU tests and the
-// sanitizers prove about the arithmetic holds for the device code.  No HIP call, no zlib.
+// gfx950 (faqcs_inflate_kernel.hip, faqcs_gunzip_kernel.hip), the way faqcs_skm.h does: every bound the decoder checks -- input that runs
+// out, a distance in front of the member, output beyond its bound -- is checked HERE, before a Sink is asked to move a byte, so what the
+// CPU tests and the sanitizers prove about the arithmetic holds for the device code.  No HIP call, no zlib.
 //
-// A Sink is who executes the decoder: one host thread (lanes() == 1) or one wave (lanes() == 64, every lane runs the same control flow
-// on the same values).  It supplies
+// A Sink is who executes the decoder: one host thread (lanes() == 1: HostSink) or one wave (lanes() == 64, every lane runs the same
+// control flow on the same values: WaveSink of faqcs_inflate_wave.h).  Its output is bytes (a BGZF member) or 16-bit symbols (a piece of
+// an ordinary gzip member: a byte, or 0x8000 | k = byte k of the MAX_DIST in front of the piece, a marker).  It supplies
 //     lane(), lanes()              who I am among the cooperating lanes
 //     sync()                       writes of any lane to the Tables are visible to every lane behind it
 //     uni(v)                       v, known to be the same in every lane (a scalar register on the device)
-//     lit(o, byte)                 output byte o of the member
-//     match(o, len, dist)          output bytes [o, o + len): byte i = output byte o - dist + (i mod dist)   (dist <= o, checked here)
-//     stored(o, src, len)          output bytes [o, o + len) = src[0 .. len)                                 (both ranges checked here)
+//     umin(v)                      the smallest v of the cooperating lanes
+//     lit(o, byte)                 output o
+//     match(o, len, dist)          outputs [o, o + len): output i = output o - dist + (i mod dist); bytes: dist <= o, checked here;
+//                                  symbols: dist <= MAX_DIST, and a source in front of output 0 is a marker
+//     stored(o, src, len)          outputs [o, o + len) = src[0 .. len)                                      (both ranges checked here)
 //     flush()                      everything handed over so far is in memory
 #pragma once
 #include <stdint.h>
@@ -29,7 +33,7 @@
 namespace faqcs_inflate {
 
 enum { ST_OK = 0, ST_E_HEADER = 1, ST_E_LENGTH = 2, ST_E_DATA = 3, ST_E_CRC = 4, ST_E_TRUNCATED = 5 }; // == FAQCS_INFLATE_*
-enum { MAX_ISIZE = 65536, MIN_MEMBER = 26, LIT_BITS = 10, DIST_BITS = 8, CL_BITS = 7, CRC_LANES = 64 };
+enum { MAX_ISIZE = 65536, MIN_MEMBER = 26, LIT_BITS = 10, DIST_BITS = 8, CL_BITS = 7, CRC_LANES = 64, MAX_DIST = 32768 };
 enum { CRC_POLY = 0xedb88320u };
 
 // What a block's decoder keeps: in LDS on the device (one per wave), on the stack on the host.  A primary table entry is
@@ -67,25 +71,49 @@ INF_HD uint32_t bgzf_member_size(const uint8_t *p, uint64_t avail)
     return 0;
 }
 
+// ---- the member header (RFC 1952) -----------------------------------------------------------------------------------------------------
+// What stands at w[0 .. have), the first bytes of a member; all: these are all the bytes there are.
+//   H_OK        a header of hlen bytes, the deflate stream behind it          H_END      not gzip: the data ends here, without an error
+//   H_HEADER    CM != 8 or a reserved FLG bit                                 H_PARTIAL  sound as far as it goes, and it ends early
+//   H_MORE      (all = false) the header is longer than the window
+enum { H_OK = 0, H_END, H_HEADER, H_PARTIAL, H_MORE };
+INF_HD int gz_header(const uint8_t *w, uint64_t have, bool all, uint32_t &hlen)
+{
+    hlen = 0;
+    const int shrt = all ? H_PARTIAL : H_MORE;
+    if (!have) return shrt;
+    if (w[0] != 31 || (have >= 2 && w[1] != 139)) return H_END;
+    if (have >= 3 && w[2] != 8) return H_HEADER;
+    if (have >= 4 && (w[3] & 0xe0u)) return H_HEADER;
+    if (have < 10) return shrt;
+    const uint32_t flg = w[3];
+    uint64_t q = 10;
+    if (flg & 4u) { // FEXTRA
+        if (have < 12) return shrt;
+        q = 12 + (uint64_t)le16(w + 10);
+    }
+    for (uint32_t bit = 8; bit <= 16; bit <<= 1) // FNAME, FCOMMENT: zero-terminated
+        if (flg & bit) {
+            while (q < have && w[q]) ++q;
+            if (q >= have) return shrt;
+            ++q;
+        }
+    if (flg & 2u) q += 2; // FHCRC: skipped, not verified
+    if (q > have) return shrt;
+    hlen = (uint32_t)q;
+    return H_OK;
+}
+
 struct Member { uint32_t data_begin, data_end, crc, isize; }; // the deflate stream is p[data_begin .. data_end), the trailer behind it
 
-// The member that fills p[0 .. size) exactly.
+// The BGZF member that fills p[0 .. size) exactly: the header in front of the trailer's eight bytes is all the header there is.
 INF_HD int parse_member(const uint8_t *p, uint64_t size, Member &m)
 {
     m.data_begin = m.data_end = m.crc = m.isize = 0;
     if (size < MIN_MEMBER || size > 65536 || bgzf_member_size(p, size) != size) return ST_E_HEADER;
-    const uint32_t flg = p[3], limit = (uint32_t)size - 8;
-    if (flg & 0xe0u) return ST_E_HEADER; // reserved flag bits
-    uint32_t q = 12 + le16(p + 10);
-    for (uint32_t bit = 8; bit <= 16; bit <<= 1) // FNAME, FCOMMENT: zero-terminated
-        if (flg & bit) {
-            while (q < limit && p[q]) ++q;
-            if (q >= limit) return ST_E_HEADER;
-            ++q;
-        }
-    if (flg & 2u) q += 2; // FHCRC
-    if (q > limit) return ST_E_HEADER;
-    m.data_begin = q; m.data_end = limit;
+    const uint32_t limit = (uint32_t)size - 8;
+    if (gz_header(p, limit, true, m.data_begin) != H_OK) return ST_E_HEADER; // (FNAME, FCOMMENT, FHCRC, the reserved bits)
+    m.data_end = limit;
     m.crc = le32(p + limit); m.isize = le32(p + limit + 4);
     return m.isize > MAX_ISIZE ? ST_E_LENGTH : ST_OK;
 }
@@ -245,14 +273,20 @@ INF_HD uint32_t multmodp(uint32_t a, uint32_t b) // a(x) b(x) modulo the gzip po
     }
     return p;
 }
-INF_HD uint32_t x8n_modp(const Tables &T, uint32_t n) // x^(8 n), n <= 65 536
+// x^(2^k) modulo the gzip polynomial, reflected, for k < n: the squaring chain
+INF_HD void x2n_fill(uint32_t *x2n, uint32_t n)
+{
+    uint32_t p = 0x40000000u; // x^1
+    for (uint32_t k = 0; k < n; ++k) { x2n[k] = p; p = multmodp(p, p); }
+}
+INF_HD uint32_t x8n_modp(const uint32_t *x2n, uint64_t n) // x^(8 n); x2n holds three entries more than n has bits
 {
     uint32_t p = 0x80000000u;
     for (uint32_t k = 3; n; n >>= 1, ++k)
-        if (n & 1u) p = multmodp(T.x2n[k], p);
+        if (n & 1u) p = multmodp(x2n[k], p);
     return p;
 }
-// the byte table and the powers: once per Tables
+// the byte table and the powers (n <= 65 536: 20 of them): once per Tables
 template <class Sink> INF_HD void crc_init(Tables &T, Sink &S)
 {
     for (uint32_t i = S.lane(); i < 256; i += S.lanes()) {
@@ -260,10 +294,7 @@ template <class Sink> INF_HD void crc_init(Tables &T, Sink &S)
         for (int k = 0; k < 8; ++k) c = (c & 1u) ? (uint32_t)CRC_POLY ^ (c >> 1) : c >> 1;
         T.crc[i] = c;
     }
-    if (S.lane() == 0) {
-        uint32_t p = 0x40000000u; // x^1
-        for (uint32_t k = 0; k < 20; ++k) { T.x2n[k] = p; p = multmodp(p, p); }
-    }
+    if (S.lane() == 0) x2n_fill(T.x2n, 20);
     S.sync();
 }
 // What slice `l` of CRC_LANES contiguous slices of text[0 .. n) adds to the CRC-32 of the whole: its own CRC multiplied by x^(8 x the bytes
@@ -281,7 +312,7 @@ INF_HD uint32_t crc_slice(const Tables &T, const uint8_t *text, uint32_t n, uint
         for (int k = 0; k < 4; ++k) c = T.crc[c & 255u] ^ (c >> 8);
     }
     for (; i < e; ++i) c = T.crc[(c ^ text[i]) & 255u] ^ (c >> 8);
-    return multmodp(x8n_modp(T, n - e), ~c);
+    return multmodp(x8n_modp(T.x2n, n - e), ~c);
 }
 
 // ---- a member ----------------------------------------------------------------------------------------------------------------------
@@ -381,15 +412,29 @@ INF_HD int inflate_member(const uint8_t *in, uint32_t begin, uint32_t end, uint3
 }
 
 // ---- the host as a Sink ------------------------------------------------------------------------------------------------------------
-struct HostSink {
-    uint8_t *out;
+template <class Sym> struct HostSink { // Sym: uint8_t, or uint16_t with markers
+    Sym *out;
     uint32_t lane() const { return 0; }
     uint32_t lanes() const { return 1; }
     void sync() {}
     uint32_t uni(uint32_t v) const { return v; }
-    void lit(uint32_t o, uint32_t v) { out[o] = (uint8_t)v; }
-    void match(uint32_t o, uint32_t len, uint32_t dist) { for (uint32_t i = 0; i < len; ++i) out[o + i] = out[o - dist + (dist >= len ? i : i % dist)]; }
-    void stored(uint32_t o, const uint8_t *src, uint32_t len) { if (len) memcpy(out + o, src, len); }
+    uint32_t umin(uint32_t v) const { return v; }
+    void lit(uint32_t o, uint32_t v) { out[o] = (Sym)v; }
+    void match(uint32_t o, uint32_t len, uint32_t dist)
+    {
+        for (uint32_t i = 0; i < len; ++i) {
+            const uint32_t x = dist >= len ? i : i % dist; // the source is output o - dist + x
+            if constexpr (sizeof(Sym) == 2) {
+                const int64_t s = (int64_t)o - dist + x;
+                out[o + i] = s < 0 ? (Sym)(0x8000u | (uint32_t)(MAX_DIST + s)) : out[s];
+            } else out[o + i] = out[o - dist + x]; // (dist <= o)
+        }
+    }
+    void stored(uint32_t o, const uint8_t *src, uint32_t len)
+    {
+        if constexpr (sizeof(Sym) == 1) { if (len) memcpy(out + o, src, len); }
+        else for (uint32_t i = 0; i < len; ++i) out[o + i] = src[i];
+    }
     void flush() {}
 };
 
@@ -399,7 +444,7 @@ inline int inflate_member_host(const uint8_t *p, uint64_t size, Tables &T, uint8
 {
     int st = parse_member(p, size, m);
     if (st) return st;
-    HostSink S{out};
+    HostSink<uint8_t> S{out};
     st = inflate_member(p, m.data_begin, m.data_end, m.isize, T, S);
     if (st) return st;
     uint32_t crc = 0;

@@ -1,6 +1,6 @@
 // faqcs_inflate_kernel.hip -- faqcs_inflate_device: BGZF members in HBM to the FASTQ text faqcs_parse_device takes (include/faqcs_mi.h,
-// DESIGN.md section 4.8).  The decoder itself is faqcs_inflate.h, the text the host statement and the sanitizer build compile too; this
-// file holds the wave that executes it and the kernels around it:
+// DESIGN.md section 4.8).  The decoder itself is faqcs_inflate.h, the text the host statement and the sanitizer build compile too, and
+// the wave that executes it is WaveSink<uint8_t> of faqcs_inflate_wave.h; this file holds the kernels around them:
 //
 //   inflate_scan      one thread per member: header and trailer, the header rules, ISIZE; block scan of ISIZE, a tile sum per block
 //   scan_tile_sums    (faqcs_pack_common.h) one block: tile prefixes, the total, the overflow decision
@@ -11,7 +11,7 @@
 //                     the output buffer itself; the CRC runs in the tail, a slice per lane
 //   inflate_finish    one block: the first bad member in input order completes info
 // No global atomic anywhere: every member's wave writes its own status word.
-#include "faqcs_inflate.h"
+#include "faqcs_inflate_wave.h"
 #include "faqcs_pack_common.h"
 
 using namespace faqcs_pack;
@@ -78,64 +78,12 @@ __global__ __launch_bounds__(SCAN_TILE) void inflate_apply(const TilePrefix *__r
     if (member_text_offset) member_text_offset[i + 1] = p;
 }
 
-// One wave as the decoder's Sink.  Literals wait one per lane -- output byte o in lane o mod 64 -- and leave together when the 64-byte
-// window is full or a copy needs them in memory.  A copy reads bytes that are all in memory before it starts (byte i of a match comes from
-// o - dist + i mod dist < o), so it is one load and one store per lane and 64 bytes, with no wait inside it; the wave reads back its own
-// stores behind a fence of wavefront scope.
-struct WaveSink {
-    uint8_t *out;
-    uint32_t l, lo, hi, mine;
-    __device__ __forceinline__ uint32_t lane() const { return l; }
-    __device__ __forceinline__ uint32_t lanes() const { return 64; }
-    __device__ __forceinline__ void sync() { __syncthreads(); } // (the block is this wave)
-    __device__ __forceinline__ uint32_t uni(uint32_t v) const { return uniu(v); }
-    __device__ __forceinline__ void flush()
-    {
-        if (hi > lo) {
-            const uint32_t a = (lo & ~63u) | l;
-            if (a >= lo && a < hi) out[a] = (uint8_t)mine;
-            lo = hi;
-        }
-    }
-    __device__ __forceinline__ void lit(uint32_t o, uint32_t v)
-    {
-        if (hi == lo) lo = hi = o;
-        if ((o & 63u) == l) mine = v;
-        hi = o + 1;
-        if ((hi & 63u) == 0) flush();
-    }
-    __device__ __forceinline__ void own_stores_visible() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); }
-    __device__ __forceinline__ void match(uint32_t o, uint32_t len, uint32_t dist)
-    {
-        flush();
-        own_stores_visible();
-        const uint8_t *src = out + o - dist;
-        uint8_t v[5];
-#pragma unroll
-        for (uint32_t k = 0; k < 5; ++k) { // (len <= 258)
-            const uint32_t i = l + 64 * k;
-            if (i < len) v[k] = src[dist >= len ? i : i % dist];
-        }
-#pragma unroll
-        for (uint32_t k = 0; k < 5; ++k) {
-            const uint32_t i = l + 64 * k;
-            if (i < len) out[o + i] = v[k];
-        }
-    }
-    __device__ __forceinline__ void stored(uint32_t o, const uint8_t *src, uint32_t len)
-    {
-        flush();
-        for (uint32_t i = l; i < len; i += 64) out[o + i] = src[i];
-    }
-};
-
 __global__ __launch_bounds__(64) void inflate_decode(const uint8_t *__restrict__ comp, const uint32_t *__restrict__ moff, const uint32_t n, const uint4 *__restrict__ hdr,
                                                      const uint32_t *__restrict__ pos, uint32_t *__restrict__ status, uint8_t *text, const faqcs_inflate_info *__restrict__ info)
 {
     __shared__ inf::Tables T;
     if (info->overflow) return;
-    WaveSink S;
-    S.l = threadIdx.x; S.out = text; S.lo = S.hi = 0; S.mine = 0;
+    WaveSink<uint8_t> S = wave_sink(text);
     inf::crc_init(T, S);
     for (uint32_t m = blockIdx.x; m < n; m += gridDim.x) {
         if (uniu(status[m])) continue; // the scan refused its header

@@ -67,6 +67,28 @@ def allowed_codes():
     return out
 
 
+# The ONE code faqcs_gunzip_* states for a stream of deflate_streams.invalid_cases() that stands alone in an ordinary gzip member, by the
+# case's kind; every kind that is not named states E_DATA.  Recorded from the library, not designed: the table is there so that a change
+# to gz_run, or one block decoder in place of gz_run and inflate_member, states what gz_run states today.  (In the "truncated" kinds that state E_DATA --
+# truncated_cl_lens, truncated_counts, truncated_len_nlen -- and in no_final_block the trailer's bytes stand behind the cut: the bits go
+# on, and what they say is wrong.)
+CATALOGUE_CODES = {E_LENGTH: ("extra_byte", "literal_past_isize", "match_past_isize", "stored_past_isize"),
+                   E_TRUNCATED: ("stored_past_input", "truncated_block_header", "truncated_code_length", "truncated_code_length_extra", "truncated_distance_extra",
+                                 "truncated_distance_symbol", "truncated_length_extra", "truncated_symbol")}
+
+
+def catalogue_code(kind):
+    assert kind in ds.INVALID_KINDS
+    return next((code for code, kinds in CATALOGUE_CODES.items() if kind in kinds), E_DATA)
+
+
+def catalogue_member(c):
+    """a case of deflate_streams.catalogue() as one gzip member: its raw stream and the trailer its BGZF member states"""
+    raw, trailer = ds.raw_stream(c)
+    crc, isize = struct.unpack("<II", trailer)
+    return gc.gz_member(b"", raw=raw, crc=crc, isize=isize)
+
+
 def zlib_verdict(raw, trailer):
     """zlib on a raw deflate stream and the eight bytes a gzip member states behind it -> "ok" or a key of VERDICT_CODES"""
     d = zlib.decompressobj(-15)

@@ -1,7 +1,7 @@
 """The catalogue of tests/gunzip_edges.py on the MI355X: every match shape against a piece start, markers of markers, markers either side
 of the resolved region, literals that wait, member edges from a later piece, the carried window, and the two catalogues of
 deflate_streams.py as gzip members -- faqcs_gunzip_device and faqcs_gunzip_stream_device against the host statement, which is checked
-against zlib first.  The wave's symbol sink (WaveSymSink of faqcs_gunzip_kernel.hip) has no host twin: the bit-for-bit comparison is its
+against zlib first.  The wave's symbol sink (WaveSink<uint16_t> of faqcs_inflate_wave.h) has no host twin: the bit-for-bit comparison is its
 test, at the shapes this catalogue feeds it.
 
 One test per family and piece size, one engine for the module.  For every case the host statement runs first and is held to zlib's text and

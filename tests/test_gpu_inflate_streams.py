@@ -2,12 +2,16 @@
 primary tables, the dynamic header's corners, hundreds of blocks in a member, and the grid of (literals waiting, match length, distance)
 that the wave's Sink (WaveSink: the part of the decoder the host never runs) has to get right.  Every byte that goes to the device here
 has been through the same decoder text on the host first, under the sanitizers, against zlib (tests/test_inflate_streams_model.py): the
-invalid cases check a refusal that is the host's before it is the device's."""
+invalid cases check a refusal that is the host's before it is the device's.  The same streams then go through faqcs_gunzip_device as ordinary
+gzip members: gz_run states the same rules a second time, and the wave's Sink is the same text with 16-bit symbols."""
 import numpy as np
 import pytest
 
 import deflate_streams as ds
+import gunzip_cases as gc
+import gunzip_edges as ge
 import inflate_cases as ic
+from test_gpu_gunzip import gunzip_device
 from test_gpu_inflate import eng, inflate_device  # noqa: F401  (eng: the module's engine fixture)
 
 pytestmark = pytest.mark.gpu
@@ -74,3 +78,26 @@ def test_invalid_cases_are_refused_as_the_host_refuses_them(eng, good):
         r = next(r for r in range(16) if (len(gt[r]) + isize) % 16 == 0)
         o = run_both(eng, [gm[r], c.member], [gt[r], bytes(isize)], c.name + " last", bad=1, code=c.code, shift=r % 5)
         assert (o["text"][ic.FRONT + len(gt[r]) + isize:] == ic.CANARY).all(), c.name + ": bytes behind the member's ISIZE were written"
+
+
+def test_the_catalogue_through_the_gzip_entry_point(eng):
+    """Every stream of the catalogue as a gzip member (gunzip_edges.catalogue_member) through faqcs_gunzip_device at pieces of 1 024 bytes:
+    the valid ones as one file of many members, each invalid one alone.  Verdict, info and text are the host statement's, which
+    tests/test_inflate_streams_model.py holds to the texts and to gunzip_edges.CATALOGUE_CODES -- asserted here once more, so that a
+    refusal is the host's before it is the device's."""
+    valid = ds.valid_cases()
+    comp, want = b"".join(ge.catalogue_member(c) for c in valid), b"".join(c.text for c in valid)
+    rc, h_info, h_text = gc.gunzip_host(eng.lib, comp, 1024, ge.ROUNDS, len(want))
+    assert rc == 0 and (h_info["error"], h_info["n_members"], h_info["n_bytes"], h_info["consumed"]) == (0, len(valid), len(want), len(comp)), h_info
+    assert bytes(h_text[gc.FRONT:gc.FRONT + len(want)]) == want
+    d_info, d_text = gunzip_device(eng, comp, 1024, ge.ROUNDS, len(want))
+    assert d_info == h_info, "device %s host %s" % (d_info, h_info)
+    assert bytes(d_text[gc.FRONT:gc.FRONT + len(want)]) == want
+    assert (d_text[:gc.FRONT] == gc.CANARY).all() and (d_text[gc.FRONT + (len(want) + 15) // 16 * 16:] == gc.CANARY).all()
+    for k, c in enumerate(ds.invalid_cases()):
+        m, cap = ge.catalogue_member(c), 65536
+        rc, h_info, _ = gc.gunzip_host(eng.lib, m, 1024, ge.ROUNDS, cap)
+        assert rc == 0 and (h_info["error"], h_info["n_members"], h_info["n_bytes"]) == (ge.catalogue_code(c.kind), 0, 0), "%s: host %s" % (c.name, h_info)
+        d_info, d_text = gunzip_device(eng, m, 1024, ge.ROUNDS, cap, shift=k % 7)
+        assert d_info == h_info, "%s: device %s host %s" % (c.name, d_info, h_info)
+        assert (d_text[:gc.FRONT] == gc.CANARY).all() and (d_text[gc.FRONT + cap:] == gc.CANARY).all(), c.name + ": bytes outside the text buffer were written"

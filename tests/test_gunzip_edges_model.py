@@ -141,6 +141,8 @@ def corpus(path):
         mode = 0 if c.kind in HEADER_FAULTS and c.name not in FAULT_BEHIND_THE_HEADER else 1
         probes += [(mode, raw, [0]), (mode, bytes([raw[0] & 254]) + raw[1:], [0])]
     files = [(piece, int(c.bad is not None), len(c.texts), b"".join(c.texts), c.comp) for c in ge.cases() if c.feed is None for piece in c.pieces]
+    # every stream of deflate_streams.catalogue() alone in a gzip member, at the piece sizes the host and the device tests run them at
+    files += [(piece, int(c.code is not None), int(c.code is None), c.text or b"", ge.catalogue_member(c)) for c in ds.catalogue() for piece in (1024, 65536)]
     # (a feed that ends with an error has delivered the blocks in front of its last one, the refused one, call by call)
     feeds = [(piece, int(c.bad is not None), b"".join(c.texts) if c.bad is None else ds.expand(c.members[0][0].items[:-1]), c.feed[0], c.comp)
              for c in ge.cases() if c.feed is not None for piece in c.pieces]

@@ -3,7 +3,8 @@ header's corners, fixed-block symbols that must be refused, hundreds of blocks i
 without a GPU.  The yardstick comes first: Python's zlib and the writer's own LZ77 expander have to agree on every case before the
 library is asked; then the writer's coverage table is held to what the catalogue promises; then the host statement, alone and as the
 middle member of a file; then the same members through the decoder text under AddressSanitizer and UBSan (tools/inflate_host_fuzz.cpp
---corpus).  tests/test_gpu_inflate_streams.py sends these very bytes to the device."""
+--corpus); last, every stream once more as an ordinary gzip member through faqcs_gunzip_host, whose block decoder (gz_run) is a second text of the same rules.
+tests/test_gpu_inflate_streams.py sends these very bytes to the device."""
 import os
 import subprocess
 import zlib
@@ -12,6 +13,8 @@ import numpy as np
 import pytest
 
 import deflate_streams as ds
+import gunzip_cases as gc
+import gunzip_edges as ge
 import inflate_cases as ic
 from faqcs_amd import _capi as capi
 
@@ -128,3 +131,24 @@ def test_the_catalogue_under_the_sanitizers(tmp_path):
     assert r.returncode == 0, (r.stdout + r.stderr).decode()[-2000:]
     want = "%d corpus members: %d accepted with zlib's text, %d refused as zlib refuses them" % (len(cases), len(ds.valid_cases()), len(ds.invalid_cases()))
     assert want.encode() in r.stdout, r.stdout.decode()[-500:]
+
+
+@pytest.mark.parametrize("piece", (1024, 65536))
+def test_the_catalogue_through_the_gzip_entry_point(lib, piece):
+    """Every stream of the catalogue alone in one gzip member (gunzip_edges.catalogue_member) through faqcs_gunzip_host: a valid one gives
+    its text, an invalid one is refused with the code of gunzip_edges.CATALOGUE_CODES -- one code per kind, among those zlib's verdict
+    allows -- and nothing is delivered.  The same members pass tools/gunzip_probe_check.cpp under the sanitizers
+    (tests/test_gunzip_edges_model.py), and tests/test_gpu_inflate_streams.py sends them to the device."""
+    allowed = ge.allowed_codes()
+    for c in ds.catalogue():
+        m = ge.catalogue_member(c)
+        rc, info, text = gc.gunzip_host(lib, m, piece, ge.ROUNDS, 65536)
+        assert rc == 0, c.name
+        if c.code is None:
+            gc.assert_case(gc.Case(c.name, m, (c.text,), None, 0, len(m), (piece,), ge.ROUNDS, frozenset()), info, text, c.name)
+            assert (text[gc.FRONT + len(c.text):] == gc.CANARY).all(), c.name + ": bytes behind the text were written"
+        else:
+            code = ge.catalogue_code(c.kind)
+            assert code in allowed[c.kind], c.name
+            assert (info["error"], info["n_members"], info["n_bytes"], info["overflow"]) == (code, 0, 0, 0), "%s (%s): %s" % (c.name, c.kind, info)
+            assert (text[:gc.FRONT] == gc.CANARY).all(), c.name + ": bytes in front of the text were written"

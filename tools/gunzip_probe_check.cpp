@@ -81,7 +81,7 @@ int main(int argc, char **argv)
             if ((gz::peek(in.get(), n, bit) & 7u) != 4u) { ++n_other; continue; }
             ++n_headers;
             const bool probe = gz::plausible_block(in.get(), n, bit);
-            gz::HostSymSink S{nullptr};
+            inf::HostSink<uint16_t> S{nullptr};
             gz::Run r;
             gz::gz_run<false>(in.get(), n, bit, bit + 1, gz::NO_BIT, gz::NO_BIT, *T, S, r);
             const bool decoder = r.status == inf::ST_OK;

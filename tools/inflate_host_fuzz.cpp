@@ -185,7 +185,7 @@ int main(int argc, char **argv)
 {
     if (argc > 2 && !strcmp(argv[1], "--corpus")) {
         T.reset(new inf::Tables);
-        inf::HostSink S{nullptr};
+        inf::HostSink<uint8_t> S{nullptr};
         inf::crc_init(*T, S);
         return run_corpus(argv[2]);
     }
@@ -193,7 +193,7 @@ int main(int argc, char **argv)
     const int n = argc > 2 ? atoi(argv[2]) : 100;
     rng.seed(seed);
     T.reset(new inf::Tables);
-    inf::HostSink S{nullptr};
+    inf::HostSink<uint8_t> S{nullptr};
     inf::crc_init(*T, S);
     const int levels[4] = {0, 1, 6, 9}, strategies[5] = {Z_DEFAULT_STRATEGY, Z_FIXED, Z_HUFFMAN_ONLY, Z_RLE, Z_FILTERED};
     const uint32_t sizes[6] = {0, 1, 2, 65280, 65535, 65536};
